@@ -2,8 +2,15 @@
 hybrid CTC/attention) on MI355X — BASELINE.json metric "utterances/sec + step-time,
 Conformer-L T=1000 batch=32 @1/2/4/8 GPU".
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2] [--fp32]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c5] [--fp32]
+                    [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...      (one rank per GPU, RCCL)
+
+A plain run sets up, warms up, times exactly K steps, writes the last timed step's outputs
+with --dump-outputs, and prints the result line.  --full adds everything else the benchmark
+measures: the roofline of the dominant GEMM (in-kernel probe over the timed steps, HIP events
+around eager launches, the committed PMC traffic), the step timed again as one rank of a DP
+job, and the CPU oracle baseline.
 
 A step = forward + backward + RCCL gradient all-reduce (N>1) + clip_grad_norm(5) + Adam +
 WarmupLR + zero_grad over one synthetic batch per rank (speech ~ N(0,1) (32, 1000, 80),
@@ -200,6 +207,37 @@ def cpu_baseline(cfg, seconds_budget=25.0):
                        f"({t:.2f} s/step)")
 
 
+DUMP_LIMIT = 64 << 20      # bytes written by --dump-outputs, all arrays together
+DUMP_PARAM_SAMPLE = 1 << 20  # elements of the parameter arena kept (a fixed, seeded sample)
+
+
+def dump_outputs(path, step_out, model):
+    """--dump-outputs: what the last timed step returned to its caller — loss, every entry of
+    stats, weight, grad_norm — and the parameters the step left behind (the arena is ~116 M
+    floats for C3, so a fixed seeded sample of DUMP_PARAM_SAMPLE elements), one
+    <name>.npy each, float32 (float64 tensors stay float64).  The arrays are views of graph
+    memory that the next replay overwrites, so this runs right after the timed steps."""
+    import numpy as np
+    loss, stats, weight, gn = step_out
+    named = [("loss", loss)] + [(f"stats_{k}", v) for k, v in sorted(stats.items())]
+    named += [("weight", weight), ("grad_norm", gn)]
+    flat = model.arena.data.detach().reshape(-1)
+    g = torch.Generator().manual_seed(20240229)
+    idx = torch.randint(0, flat.numel(), (min(DUMP_PARAM_SAMPLE, flat.numel()),), generator=g)
+    named.append(("params_sample", flat[idx.to(flat.device)]))
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, v in named:
+        if v is None:
+            continue
+        t = torch.as_tensor(v).detach()
+        t = t.to("cpu", torch.float64 if t.dtype == torch.float64 else torch.float32)
+        total += t.numel() * t.element_size()
+        if total > DUMP_LIMIT:
+            raise RuntimeError(f"--dump-outputs: more than {DUMP_LIMIT} bytes at {name}")
+        np.save(os.path.join(path, name + ".npy"), t.numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -207,7 +245,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)  # after 10 warm-up steps
     ap.add_argument("--config", default="c3", choices=["c3", "c2", "c5"])
     ap.add_argument("--fp32", action="store_true", help="exact-f32 MFMA instead of bf16 AMP")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the roofline of the "
+                         "dominant GEMM, the DP rehearsal and the CPU oracle baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (and a seeded sample of the parameters "
+                         "after it) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full, skip the CPU baseline")
     ap.add_argument("--profile-steps", type=int, default=0)
     ap.add_argument("--graph-dp", action="store_true",
                     help="(kept for old command lines) with N > 1 the step incl. its RCCL all-reduces "
@@ -217,8 +261,8 @@ def main():
     ap.add_argument("--eager", action="store_true", help="launch every kernel from Python each step "
                     "(default: the step is captured once as a hipGraph and replayed)")
     ap.add_argument("--no-dp-rehearsal", action="store_true",
-                    help="at N=1, skip the second timing of the step as one rank of a DP job (a "
-                         "world-1 RCCL group with every collective of an N-GPU step)")
+                    help="with --full at N=1, skip the second timing of the step as one rank of a DP "
+                         "job (a world-1 RCCL group with every collective of an N-GPU step)")
     ap.add_argument("--dp-rehearsal-steps", type=int, default=20)
     args = ap.parse_args()
 
@@ -293,45 +337,32 @@ def main():
             el = float(t.item())
         return el, sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(steps)), last
 
-    # in-kernel span probe of the dominant GEMM; captured into the graph, so it measures
-    # every replay; reset after warmup so only the timed region counts
-    probe = hip_ops.KernelProbe(["conv2_gemm"], dev)
+    # --full: in-kernel span probe of the dominant GEMM; captured into the graph, so it
+    # measures every replay; reset after warmup so only the timed region counts
+    probe = hip_ops.KernelProbe(["conv2_gemm"], dev) if args.full else None
     hip_ops.PROBE = probe
     for _ in range(max(args.warmup, 0 if eager else 3)):
         step()
     torch.cuda.synchronize()
     sync_capture_mode(runner, world)
-    probe.reset()
+    if probe is not None:
+        probe.reset()
     # per-step HIP events on the step's stream (median step time)
-    elapsed, step_ms, (loss, stats, weight, gn) = timed(step, args.steps)
+    elapsed, step_ms, last = timed(step, args.steps)
     hip_ops.PROBE = None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, model)
+    loss, stats, weight, gn = last
     step_mode = runner.mode or "eager"
     ms = elapsed / args.steps * 1e3
     utt = cfg["B"] * world * args.steps / elapsed
-    conv_ms, n_conv = probe.mean_ms("conv2_gemm")
-    # the same launch timed with HIP events on its stream: eager forwards of the subsampling
-    # block after the timed region (events cannot sit inside the captured graph)
-    ev_probe = hip_ops.EventProbe(["conv2_gemm"])
-    hip_ops.PROBE = ev_probe
-    with torch.no_grad():
-        for i in range(6):
-            if i == 1:
-                ev_probe.reset()  # first launch warms the eager path
-            model.encoder.embed(batch["speech"], 0)
-    conv_ev_ms, n_ev = ev_probe.mean_ms("conv2_gemm")
-    hip_ops.PROBE = None
     med_ms = step_ms[len(step_ms) // 2]
     B, T = cfg["B"], cfg["T"]
-    T1, F1 = (T - 3) // 2 + 1, (80 - 3) // 2 + 1
-    T2, F2 = (T1 - 3) // 2 + 1, (F1 - 3) // 2 + 1
-    C = cfg["encoder_conf"]["output_size"]
-    conv_flop = 2.0 * B * T2 * F2 * C * 9 * C
     dtype = "bf16" if amp else "f32"
-    achieved = conv_flop / (conv_ms * 1e-3) / 1e12
     loss_v = float(loss.item())
-    traffic, traffic_src, traffic_same = pmc_traffic() if (args.config == "c3" and amp) else (None, None, False)
+    roof = roofline(args, cfg, model, batch, probe, dtype) if args.full else None
     rehearsal = None
-    if world == 1 and not args.no_dp_rehearsal and args.dp_rehearsal_steps > 0:
+    if args.full and world == 1 and not args.no_dp_rehearsal and args.dp_rehearsal_steps > 0:
         rehearsal = dp_rehearsal(model, opt, sched, batch, maxlens, cfg, eager, args, timed)
     if rank == 0:
         out = {
@@ -348,19 +379,7 @@ def main():
                 **({"diag_dropout": float(os.environ["EA_BENCH_DIAG_DROPOUT"])}
                    if "EA_BENCH_DIAG_DROPOUT" in os.environ else {})},
             "model_tflops_per_s": round(cfg["gflop_per_step"] * world / (ms * 1e-3) / 1e3, 2),
-            "roofline": {"bound": "mfma", "kernel": ("gemm_pipe" if GEMM_PIPE else "gemm_bf16_lds") +
-                         f" bf16 conv2 implicit GEMM (subsampling forward, M={B * T2 * F2} N={C} K={9 * C})",
-                         "achieved": round(achieved, 2), "peak": PEAK[dtype], "unit": "TFLOP/s",
-                         "frac": round(achieved / PEAK[dtype], 4), "traffic": traffic,
-                         "traffic_unit": "bytes/launch (HBM, PMC)", "traffic_source": traffic_src,
-                         "traffic_measured_on_this_build": traffic_same,
-                         "algorithmic_bytes": int(2 * (B * T1 * F1 * C + C * 9 * C + B * T2 * F2 * C)),
-                         "launch_ms": round(conv_ms, 4), "launches": n_conv,
-                         "timing": "achieved/frac from the in-kernel probe (first-block start to "
-                                   "last-block end, every timed replay); frac_events from HIP "
-                                   "events around eager launches on the launch stream",
-                         "launch_ms_events": round(conv_ev_ms, 4), "launches_events": n_ev,
-                         "frac_events": round(conv_flop / (conv_ev_ms * 1e-3) / 1e12 / PEAK[dtype], 4)},
+            **({"roofline": roof} if roof is not None else {}),
             "step_mode": step_mode,
             "step_ms_median": round(med_ms, 3),
             "step_ms_p10_p90": [round(step_ms[len(step_ms) // 10], 3), round(step_ms[(9 * len(step_ms)) // 10], 3)],
@@ -369,12 +388,53 @@ def main():
         }
         if rehearsal is not None:
             out["dp_rehearsal"] = rehearsal
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg)
             out["speedup_vs_cpu"] = round(utt / out["cpu_baseline"]["value"], 1)
         emit(out)
     if world > 1:
         dist.destroy_process_group()
+
+
+def roofline(args, cfg, model, batch, probe, dtype):
+    """--full: the dominant GEMM (conv2 forward of the subsampling block) against the MFMA
+    peak — from the in-kernel probe over the timed steps, and from HIP events around eager
+    launches after them — with the HBM traffic of the committed PMC pass."""
+    from espnet_amd import hip_ops
+    from espnet_amd._lib import GEMM_PIPE
+    conv_ms, n_conv = probe.mean_ms("conv2_gemm")
+    # the same launch timed with HIP events on its stream: eager forwards of the subsampling
+    # block after the timed region (events cannot sit inside the captured graph)
+    ev_probe = hip_ops.EventProbe(["conv2_gemm"])
+    hip_ops.PROBE = ev_probe
+    with torch.no_grad():
+        for i in range(6):
+            if i == 1:
+                ev_probe.reset()  # first launch warms the eager path
+            model.encoder.embed(batch["speech"], 0)
+    conv_ev_ms, n_ev = ev_probe.mean_ms("conv2_gemm")
+    hip_ops.PROBE = None
+    B, T = cfg["B"], cfg["T"]
+    T1, F1 = (T - 3) // 2 + 1, (80 - 3) // 2 + 1
+    T2, F2 = (T1 - 3) // 2 + 1, (F1 - 3) // 2 + 1
+    C = cfg["encoder_conf"]["output_size"]
+    conv_flop = 2.0 * B * T2 * F2 * C * 9 * C
+    achieved = conv_flop / (conv_ms * 1e-3) / 1e12
+    traffic, traffic_src, traffic_same = (pmc_traffic() if (args.config == "c3" and dtype == "bf16")
+                                          else (None, None, False))
+    return {"bound": "mfma", "kernel": ("gemm_pipe" if GEMM_PIPE else "gemm_bf16_lds") +
+            f" bf16 conv2 implicit GEMM (subsampling forward, M={B * T2 * F2} N={C} K={9 * C})",
+            "achieved": round(achieved, 2), "peak": PEAK[dtype], "unit": "TFLOP/s",
+            "frac": round(achieved / PEAK[dtype], 4), "traffic": traffic,
+            "traffic_unit": "bytes/launch (HBM, PMC)", "traffic_source": traffic_src,
+            "traffic_measured_on_this_build": traffic_same,
+            "algorithmic_bytes": int(2 * (B * T1 * F1 * C + C * 9 * C + B * T2 * F2 * C)),
+            "launch_ms": round(conv_ms, 4), "launches": n_conv,
+            "timing": "achieved/frac from the in-kernel probe (first-block start to "
+                      "last-block end, every timed replay); frac_events from HIP "
+                      "events around eager launches on the launch stream",
+            "launch_ms_events": round(conv_ev_ms, 4), "launches_events": n_ev,
+            "frac_events": round(conv_flop / (conv_ev_ms * 1e-3) / 1e12 / PEAK[dtype], 4)}
 
 
 def sync_capture_mode(runner, world):
@@ -488,6 +548,8 @@ def run_c5(args, world, rank, dev):
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, (loss, stats, weight, gn), model)
     tot = torch.tensor([elapsed, n_utt, n_frames, n_padded], dtype=torch.float64, device=dev)
     if world > 1:
         mx = tot[:1].clone()

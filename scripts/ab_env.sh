@@ -5,7 +5,7 @@
 set -o pipefail
 export TMPDIR=/tmp
 O=gpurun_out/$1; VAR=$2; VALS=$3; R=${4:-2}
-ARGS="--no-cpu-baseline"; [ "${DP:-0}" = 1 ] || ARGS="$ARGS --no-dp-rehearsal"
+ARGS=""; [ "${DP:-0}" = 1 ] && ARGS="--full --no-cpu-baseline"
 mkdir -p "$O"
 for r in $(seq 1 $R); do
   for v in $VALS; do
