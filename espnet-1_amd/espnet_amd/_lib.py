@@ -1,7 +1,7 @@
 """ctypes binding of libespnet_amd.so (the C ABI in include/espnet_amd.h).
 
-The argument types are derived from the header's prototypes, so the Python side and the
-C ABI cannot drift.  Loading fails loudly when the library is missing: there is no CPU
+The argument types, the structures and the enumerators are all parsed from the header, so
+the Python side and the C ABI cannot drift.  Loading fails loudly when the library is missing: there is no CPU
 or PyTorch fallback for any op on the hot path.
 """
 from __future__ import annotations
@@ -21,73 +21,76 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "lib", os.environ.get("EA_LIB_NAME", "libespnet_amd.so"))
 HEADER = os.path.join(os.path.dirname(os.path.dirname(_PKG)), "include", "espnet_amd.h")
 
-F32, BF16 = 0, 1
 GEMM_PIPE = int(os.environ.get("EA_GEMM_PIPE", "1"))
-ACT_NONE, ACT_SWISH, ACT_RELU = 0, 1, 2
-EPI_STORE, EPI_ACT, EPI_RESID, EPI_DACT = 0, 1, 2, 3
-ERR_BAD_ARG = 1000
-
-
-class Epilogue(ctypes.Structure):
-    _fields_ = [
-        ("kind", ctypes.c_int), ("act", ctypes.c_int),
-        ("alpha", ctypes.c_float), ("beta", ctypes.c_float), ("post_scale", ctypes.c_float),
-        ("rscale", ctypes.c_float), ("drop_p", ctypes.c_float),
-        ("seed", ctypes.c_ulonglong),
-        ("bias", ctypes.c_void_p),
-        ("aux", ctypes.c_void_p), ("aux_dtype", ctypes.c_int), ("ldaux", ctypes.c_long),
-        ("resid", ctypes.c_void_p), ("ldr", ctypes.c_long),
-    ]
-
-
-class GroupGemm(ctypes.Structure):
-    """ea_group_gemm: one problem of ea_gemm_grouped."""
-    _fields_ = [("A", ctypes.c_void_p), ("B", ctypes.c_void_p), ("C", ctypes.c_void_p),
-                ("lda", ctypes.c_long), ("ldb", ctypes.c_long), ("ldc", ctypes.c_long),
-                ("M", ctypes.c_int), ("N", ctypes.c_int), ("K", ctypes.c_int), ("beta", ctypes.c_float)]
-
-
-class ColsumProb(ctypes.Structure):
-    """ea_colsum_prob: one column-sum problem of ea_colsum_grouped."""
-    _fields_ = [("x", ctypes.c_void_p), ("part", ctypes.c_void_p), ("ld", ctypes.c_long),
-                ("rows", ctypes.c_int), ("n", ctypes.c_int), ("dtype", ctypes.c_int), ("rpp", ctypes.c_int)]
-
-
-class ReduceProb(ctypes.Structure):
-    """ea_reduce_prob: one ordered partial-sum reduction of ea_reduce_grouped."""
-    _fields_ = [("part", ctypes.c_void_p), ("out", ctypes.c_void_p), ("stride", ctypes.c_long),
-                ("nparts", ctypes.c_int), ("n", ctypes.c_int), ("accumulate", ctypes.c_int)]
-
-
-SCHED_CONSTANT, SCHED_WARMUP = 0, 1
-CONV_FWD, CONV_DGRAD, CONV_WGRAD = 1, 2, 3
-
-
-class ConvGeo(ctypes.Structure):
-    """ea_conv_geo: phase-split implicit-GEMM geometry of the subsampling conv2."""
-    _fields_ = [("mode", ctypes.c_int), ("B", ctypes.c_int), ("T2", ctypes.c_int), ("F2", ctypes.c_int),
-                ("C", ctypes.c_int), ("P", ctypes.c_int), ("nI", ctypes.c_int * 2), ("nJ", ctypes.c_int * 2),
-                ("a", ctypes.c_int), ("e", ctypes.c_int), ("plane", ctypes.c_long * 4), ("zero", ctypes.c_long)]
-
-
-class LrSchedule(ctypes.Structure):
-    _fields_ = [("kind", ctypes.c_int), ("warmup_steps", ctypes.c_float), ("base_lr", ctypes.c_double)]
-
-
-# ea_opt_state (device memory, 40 B): step i64 | lr bc1 bc2_sqrt coef last_norm f32 | skip i32 |
-# next_lr f32 | pad
-OPT_STATE_BYTES = 40
-OPT_STATE_NEXT_LR = 8  # float index of next_lr
-
 
 _CTYPES = {
     "int": ctypes.c_int,
     "long": ctypes.c_long,
+    "long long": ctypes.c_longlong,
     "float": ctypes.c_float,
     "double": ctypes.c_double,
     "unsigned long long": ctypes.c_ulonglong,
     "unsigned int": ctypes.c_uint,
 }
+
+
+def _source(path):
+    src = open(path).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    return re.sub(r"//[^\n]*", "", src)
+
+
+def _scalar_ctype(base: str, decl: str):
+    if base not in _CTYPES:
+        raise TypeError(f"unsupported C type in header: {decl!r}")
+    return _CTYPES[base]
+
+
+def _member_fields(decl: str):
+    """One struct member declaration -> [(name, ctype)]: a scalar, a comma list
+    (`int B, T2;`), fixed arrays (`int nI[2], nJ[2];`) or one pointer (-> c_void_p)."""
+    text = re.sub(r"\bconst\b", "", decl).strip()
+    m = re.fullmatch(r"[\w\s]+\*\s*(\w+)", text)
+    if m:
+        return [(m.group(1), ctypes.c_void_p)]
+    first, *rest = (d.strip() for d in text.split(","))
+    base, _, first = first.rpartition(" ")
+    ctype = _scalar_ctype(" ".join(base.split()), decl)
+    fields = []
+    for d in [first] + rest:
+        m = re.fullmatch(r"(\w+)(?:\[(\d+)\])?", d)
+        if not m:
+            raise TypeError(f"unsupported struct member in header: {decl!r}")
+        fields.append((m.group(1), ctype * int(m.group(2)) if m.group(2) else ctype))
+    return fields
+
+
+def parse_abi(path: str = HEADER):
+    """-> ({struct name: ctypes.Structure class}, {enumerator: value}) for every
+    `typedef struct ea_* { ... } ea_*;` and `enum { EA_* = n, ... };` of the header."""
+    src = _source(path)
+    structs, enums = {}, {}
+    for m in re.finditer(r"\btypedef\s+struct\s+(ea_\w+)\s*\{([^}]*)\}\s*\1\s*;", src):
+        fields = [f for d in m.group(2).split(";") if d.strip() for f in _member_fields(d)]
+        structs[m.group(1)] = type(m.group(1), (ctypes.Structure,), {"_fields_": fields})
+    for m in re.finditer(r"\benum\s*\{([^}]*)\}\s*;", src):
+        for item in filter(None, (x.strip() for x in m.group(1).split(","))):
+            e = re.fullmatch(r"(EA_\w+)\s*=\s*(-?\d+)", item)
+            if not e:
+                raise TypeError(f"unsupported enumerator in header: {item!r}")
+            enums[e.group(1)] = int(e.group(2))
+    return structs, enums
+
+
+STRUCTS, ENUMS = parse_abi()
+Epilogue, GroupGemm, ColsumProb, ReduceProb, ConvGeo, LrSchedule, _OptState = (
+    STRUCTS["ea_" + n] for n in ("epilogue", "group_gemm", "colsum_prob", "reduce_prob", "conv_geo",
+                                 "lr_schedule", "opt_state"))
+# every enumerator under its name without the EA_ prefix: F32, BF16, ERR_BAD_ARG, ACT_*, EPI_*,
+# CONV_*, SCHED_*
+globals().update({k[3:]: v for k, v in ENUMS.items()})
+OPT_STATE_BYTES = ctypes.sizeof(_OptState)  # ea_opt_state lives in device memory
+OPT_STATE_NEXT_LR = _OptState.next_lr.offset // 4  # float index of next_lr
 
 
 def _arg_ctype(decl: str):
@@ -97,17 +100,12 @@ def _arg_ctype(decl: str):
     if "*" in decl:
         return ctypes.c_void_p
     base = re.sub(r"\bconst\b", "", decl).strip()
-    base = " ".join(base.split()[:-1])  # drop the parameter name
-    if base not in _CTYPES:
-        raise TypeError(f"unsupported C type in header: {decl!r}")
-    return _CTYPES[base]
+    return _scalar_ctype(" ".join(base.split()[:-1]), decl)  # without the parameter name
 
 
 def parse_header(path: str = HEADER):
     """-> {name: [ctypes arg types]} for every `int ea_*(...)` prototype."""
-    src = open(path).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    src = re.sub(r"//[^\n]*", "", src)
+    src = _source(path)
     protos = {}
     for m in re.finditer(r"\bint\s+(ea_\w+)\s*\(([^)]*)\)\s*;", src):
         name, args = m.group(1), m.group(2)
@@ -118,6 +116,17 @@ def parse_header(path: str = HEADER):
 
 class HipError(RuntimeError):
     pass
+
+
+_DT = {torch.float32: F32, torch.bfloat16: BF16}  # noqa: F821  (bound from ENUMS above)
+
+
+def dt(t: torch.Tensor) -> int:
+    """The EA_F32 / EA_BF16 code of a tensor's element type."""
+    try:
+        return _DT[t.dtype]
+    except KeyError:
+        raise HipError(f"unsupported dtype {t.dtype}") from None
 
 
 class _Lib:

@@ -14,12 +14,13 @@ import os
 import torch
 
 from .. import hip_ops as ops
+from ..hip_ops import ptr
 from .._lib import (ACT_NONE, ACT_RELU, ACT_SWISH, EPI_ACT, EPI_DACT, EPI_RESID, EPI_STORE,
                     lib)
 
 __all__ = ["Bound", "rup", "empty", "ops", "lib", "EPI_ACT", "EPI_DACT", "EPI_RESID",
            "EPI_STORE", "ACT_NONE", "ACT_RELU", "ACT_SWISH", "site_seed", "attn_fwd", "attn_bwd",
-           "LayerNormFn", "ln_fwd", "ln_bwd", "math", "F32", "fused_attn_ok", "attn_dmask", "ptr",
+           "LayerNormFn", "ln_fwd", "ln_bwd", "math", "F32", "fused_attn_ok", "attn_dmask",
            "attn_fused_bwd", "dv_buf", "drop_arg", "site_dv", "multisequential_draw"]
 
 F32 = torch.float32
@@ -42,10 +43,6 @@ def fused_attn_ok(cd, dk, T1, T2) -> bool:
     """The fused attention kernels (relattn.hip) take bf16 operands and head dim 64 (any
     lengths); other cases use the unfused path."""
     return FUSED_ATTN and cd == torch.bfloat16 and dk == 64 and T1 >= 1 and T2 >= 1
-
-
-def ptr(t) -> int:
-    return 0 if t is None else t.data_ptr()
 
 
 def attn_dmask(rows, T2, p, device):

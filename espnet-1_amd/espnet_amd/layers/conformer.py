@@ -19,7 +19,7 @@ import torch
 from torch import nn
 
 from .common import (ACT_SWISH, EPI_ACT, EPI_DACT, EPI_RESID, EPI_STORE, F32, Bound, attn_bwd, attn_dmask, dbd_layout,
-                     attn_fused_bwd, attn_fwd, empty, fused_attn_ok, lib, ln_bwd, ln_fwd, math, ops, ptr, rup,
+                     attn_fused_bwd, attn_fwd, empty, fused_attn_ok, lib, ln_bwd, ln_fwd, math, ops, rup,
                      site_seed, dv_buf, drop_arg, site_dv)
 
 
@@ -218,7 +218,7 @@ class ConformerBlockFn(torch.autograd.Function):
             lib.ea_attn_fused_fwd2(B, H, T, T, dk, qkv.data_ptr(), 3 * d, qkv[:, d:].data_ptr(), 3 * d,
                                    qkv[:, 2 * d:].data_ptr(), 3 * d, b.f(A + "pos_bias_u").data_ptr(),
                                    b.f(A + "pos_bias_v").data_ptr(), pp.data_ptr(), d, olens.data_ptr(), 0,
-                                   scale, float(pa), sd(3), O.data_ptr(), d, lse.data_ptr(), ptr(dmask), ldm,
+                                   scale, float(pa), sd(3), O.data_ptr(), d, lse.data_ptr(), ops.ptr(dmask), ldm,
                                    ops.stream())
             ldT = 0
             s_core = ("fused", lse, dmask, ldm)
@@ -335,7 +335,7 @@ class ConformerBlockFn(torch.autograd.Function):
         fuse = FUSE_DW_GLU and K in (3, 5, 7, 15, 31) and g2.dtype == torch.bfloat16
         if fuse:
             # the GLU backward inside the depthwise conv's input-gradient store (no f32 dglu)
-            w, wn = ops._ws(dev, B * ((T + 31) // 32) * d * (K + 1) + 1024)
+            w, wn = ops.f32_ws(dev, B * ((T + 31) // 32) * d * (K + 1) + 1024)
             lib.ea_dwconv_glu_bwd(B, T, d, K, ops.ptr(glu), b.f(C + "depthwise_conv.weight").data_ptr(),
                                   dy.data_ptr(), g2.data_ptr(), dg2.data_ptr(),
                                   b.g(C + "depthwise_conv.weight").data_ptr(),
@@ -345,7 +345,7 @@ class ConformerBlockFn(torch.autograd.Function):
                 glu = empty(N, d, device=dev)
                 lib.ea_glu_fwd(N, d, g2.data_ptr(), ops.dt(g2), glu.data_ptr(), 0, ops.stream())
             dglu = empty(N, d, device=dev)
-            w, wn = ops._ws(dev, B * ((T + 31) // 32) * d * (K + 1) + 1024)
+            w, wn = ops.f32_ws(dev, B * ((T + 31) // 32) * d * (K + 1) + 1024)
             lib.ea_dwconv_bwd(B, T, d, K, glu.data_ptr(), b.f(C + "depthwise_conv.weight").data_ptr(),
                               dy.data_ptr(), dglu.data_ptr(), b.g(C + "depthwise_conv.weight").data_ptr(),
                               b.g(C + "depthwise_conv.bias").data_ptr(), 1, w, wn, ops.stream())

@@ -16,7 +16,7 @@ import torch
 from torch import nn
 
 from .common import (ACT_RELU, EPI_ACT, EPI_DACT, EPI_RESID, EPI_STORE, F32, Bound, attn_bwd,
-                     attn_dmask, attn_fused_bwd, attn_fwd, empty, fused_attn_ok, lib, ln_bwd, ln_fwd, ops, ptr,
+                     attn_dmask, attn_fused_bwd, attn_fwd, empty, fused_attn_ok, lib, ln_bwd, ln_fwd, ops,
                      site_seed, dv_buf, drop_arg, site_dv)
 
 
@@ -30,7 +30,7 @@ def _mha_fwd(q, k, v, *, B, H, T1, T2, dk, ldq, ldk, ldv, klen, causal, scale, p
         dmask, ldm = attn_dmask(B * H * T1, T2, p, q.device)
         lib.ea_attn_fused_fwd2(B, H, T1, T2, dk, q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv,
                                None, None, None, 0, klen.data_ptr(), int(causal), scale, float(p), seed,
-                               O.data_ptr(), H * dk, lse.data_ptr(), ptr(dmask), ldm, ops.stream())
+                               O.data_ptr(), H * dk, lse.data_ptr(), ops.ptr(dmask), ldm, ops.stream())
         return O, ("fused", O, lse, dmask, ldm)
     O, P, Pd, ldT = attn_fwd(q, k, v, B=B, H=H, T1=T1, T2=T2, dk=dk, ldq=ldq, ldk=ldk, ldv=ldv, klen=klen,
                              causal=causal, scale=scale, p=p, seed=seed, cd=cd)

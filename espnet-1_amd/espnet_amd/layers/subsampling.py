@@ -203,7 +203,7 @@ class SubsampleFn(torch.autograd.Function):
         if probe is not None:
             probe.begin("conv2_gemm")
         epi = ops.make_epi(EPI_ACT, bias=b.f("conv.2.bias"), act=ACT_RELU)
-        ws = ops.workspace(ops._SPLITK_WS, dev)
+        ws = ops.splitk_ws(dev)
         lib.ea_gemm_conv(ctypes.byref(geo), 1, 1, P2, C, 9 * C, x1p.data_ptr(), C, w2.data_ptr(), 9 * C,
                          x2.data_ptr(), ops.dt(x2), C, ctypes.byref(epi), ws.data_ptr(), ws.numel(), ops.stream())
         if probe is not None:
@@ -250,7 +250,7 @@ class SubsampleFn(torch.autograd.Function):
             dw2 = empty(C, 9 * C, device=dev)
             geo, _, _, _ = phase_geo(B, T1, F1, T2, F2, C, CONV_WGRAD, zero=P1 * C)
             epi = ops.make_epi()
-            ws_side = ops.workspace(ops._SPLITK_WS, dev)
+            ws_side = ops.splitk_ws(dev)
             lib.ea_gemm_conv(ctypes.byref(geo), 0, 0, C, 9 * C, K2, dx2.data_ptr(), C, x1p.data_ptr(), C,
                              dw2.data_ptr(), ops.dt(dw2), 9 * C, ctypes.byref(epi), ws_side.data_ptr(),
                              ws_side.numel(), ops.stream())
@@ -260,7 +260,7 @@ class SubsampleFn(torch.autograd.Function):
         # stays on chip: each tile's epilogue multiplies it by conv1's input patches
         # (ea_gemm_conv_w1), so dx1 is never written and conv1's weight / bias gradients are
         # the sum of per-tile partials
-        ws = ops.workspace(ops._SPLITK_WS, dev)
+        ws = ops.splitk_ws(dev)
         fuse = FUSE_CONV1_WGRAD
         kmaj = DGRAD_KMAJOR and fuse and pos1 is not None and MERGED_DGRAD
         if kmaj:  # W2k: (Co, Ci*9) -> (Ci*9, Co), every output channel's K = (tap, co) row dense
@@ -314,7 +314,7 @@ class SubsampleFn(torch.autograd.Function):
                                       b.g("conv.0.bias").data_ptr(), ops.stream())
         else:
             with ops.wgrad(dx1p, feats, launches=True):
-                w, wn = ops._ws(dev, 1024 * 10 * C)
+                w, wn = ops.f32_ws(dev, 1024 * 10 * C)
                 lib.ea_conv1_wgrad(B, T, Fin, C, feats.data_ptr(), dx1p.data_ptr(), ops.dt(dx1p),
                                    b.g("conv.0.weight").data_ptr(), b.g("conv.0.bias").data_ptr(), w, wn, ops.stream())
         ops.grad_ready(b)

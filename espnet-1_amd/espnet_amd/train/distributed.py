@@ -22,7 +22,7 @@ from typing import Dict, List
 import torch
 import torch.distributed as dist
 
-from .. import hip_ops
+from .. import deferred, hip_ops
 
 class ArenaDataParallel:
     def __init__(self, model, bucket_mb: float = None, group=None, overlap: bool = True,
@@ -139,7 +139,7 @@ class ArenaDataParallel:
         self._pending = [set(m) for m in self._bucket_mods]
         self._works = []
         if self.overlap and self.active:
-            hip_ops.GRAD_READY = self.grad_ready
+            deferred.GRAD_READY = self.grad_ready
 
     def grad_ready(self, prefix: str):
         """A block's backward is done (hip_ops.grad_ready).  Its deferred weight-gradient
@@ -194,7 +194,7 @@ class ArenaDataParallel:
 
     def allreduce_grads(self):
         """Finish the step's gradient reduction (launch what the hooks did not, wait all)."""
-        hip_ops.GRAD_READY = None
+        deferred.GRAD_READY = None
         hip_ops.flush_deferred()
         hip_ops.join_wgrad()
         if self._pending is None:

@@ -28,6 +28,7 @@ from typing import Dict, Optional
 
 import torch
 
+from .. import deferred
 from ..layers import common
 from ..layers.common import multisequential_draw as layerdrop_draw
 from .trainer import Trainer
@@ -255,8 +256,7 @@ class CapturedTrainStep:
         """A capture that raised mid-step leaves per-pass host state behind (the deferred
         queues are dropped by their context; the DP grad-ready hook and bucket bookkeeping
         are not): clear it so the eager step starts clean."""
-        from .. import hip_ops
-        hip_ops.GRAD_READY = None
+        deferred.GRAD_READY = None
         if self.dp is not None:
             self.dp._pending = None
             self.dp._works = []

@@ -15,7 +15,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "..", "espnet-1
 from goldens import is_null_grad, regenerate_sized  # noqa: E402
 from test_model_build import build  # noqa: E402
 import test_benched_shapes_gpu as T  # noqa: E402
-from espnet_amd import hip_ops as ops  # noqa: E402
+from espnet_amd import deferred, streams  # noqa: E402
 
 WATCH = ("decoder.decoders.1.norm3.weight", "decoder.decoders.1.norm3.bias",
          "decoder.decoders.1.feed_forward.w_1.weight", "decoder.decoders.1.feed_forward.w_1.bias",
@@ -46,13 +46,10 @@ def main():
     del m
     g0 = run("default", x_grads)
     run("default again", x_grads, g0)
-    ops.DEFER_REDUCE = False
+    deferred.DEFER_REDUCE = False
     run("no deferred reductions", x_grads)
-    ops.DEFER_REDUCE = True
-    ops.REDUCE_SIDE = False
-    run("reductions serial", x_grads)
-    ops.REDUCE_SIDE = True
-    ops.OVERLAP_WGRAD = False
+    deferred.DEFER_REDUCE = True
+    streams.WGRAD.enabled = False
     run("no side stream", x_grads)
 
 

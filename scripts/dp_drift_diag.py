@@ -30,14 +30,14 @@ def worker(rank, world, init, args):
     import torch.distributed as dist
     import test_dp_capture_gpu as C
     import test_dp_ragged_gpu as R
-    from espnet_amd import hip_ops
+    from espnet_amd import streams
     from espnet_amd.train.distributed import ArenaDataParallel
     from espnet_amd.train.trainer import Trainer
     import espnet_amd.train.distributed as dmod
     torch.cuda.set_device(0)
     dist.init_process_group("gloo", init_method=f"file://{init}", rank=rank, world_size=world)
     if args.no_overlap:
-        hip_ops.OVERLAP_WGRAD = False
+        streams.WGRAD.enabled = False
     glob = R._global_batches(6)
     shards = [R._shard(glob[0], 0, world)] * 6 if rank == 0 else [R._shard(glob[i % 2], 1, world) for i in range(6)]
     real_ar = dist.all_reduce
@@ -114,7 +114,7 @@ def fresh_worker(rank, world, init, args, out):
         torch.cuda.max_memory_reserved = lambda *a, **k: 0  # (no statistics from a pluggable allocator)
     import test_dp_capture_gpu as C
     import test_dp_ragged_gpu as R
-    from espnet_amd import hip_ops
+    from espnet_amd import streams
     from espnet_amd.train.distributed import ArenaDataParallel
     from espnet_amd.train.distributed_utils import DistributedOption
     from espnet_amd.train.reporter import Reporter
@@ -123,9 +123,9 @@ def fresh_worker(rank, world, init, args, out):
     torch.cuda.set_device(0)
     dist.init_process_group("gloo", init_method=f"file://{init}", rank=rank, world_size=world)
     if args.no_overlap:
-        hip_ops.OVERLAP_WGRAD = False
+        streams.WGRAD.enabled = False
     if args.no_aux:
-        hip_ops.OVERLAP_AUX = False
+        streams.AUX.enabled = False
     real_ar = dist.all_reduce
     snaps = []
 

@@ -10,7 +10,7 @@ there, name the backward segment that produced the difference.
 
 --poison    every torch.empty / empty_like / new_empty float buffer starts as NaN (set before the
             package is imported): a kernel that reads an element nobody wrote turns NaN
---delay-ns  hold every side / auxiliary stream segment that long (hip_ops.DEBUG_DELAY_NS)
+--delay-ns  hold every side / auxiliary stream segment that long (streams.DEBUG_DELAY_NS)
 --serial    the main stream joins every side / auxiliary segment at its end
 --hog MB    a second stream copies MB-sized buffers back to back during every step (HBM and
             CU contention, as a second process on the card gives)
@@ -106,9 +106,9 @@ def main():
     args = ap.parse_args()
     if args.poison:
         poison()
-    from espnet_amd import hip_ops
-    hip_ops.DEBUG_DELAY_NS = args.delay_ns
-    hip_ops.DEBUG_SERIAL = args.serial
+    from espnet_amd import streams
+    streams.DEBUG_DELAY_NS = args.delay_ns
+    streams.DEBUG_SERIAL = args.serial
     torch.cuda.set_device(0)
     if args.dp:
         import torch.distributed as dist
@@ -122,8 +122,8 @@ def main():
     if args.modes:
         res = []
         for mode in args.modes.split(","):
-            hip_ops.DEBUG_DELAY_NS = 300_000 if "delay" in mode else args.delay_ns
-            hip_ops.DEBUG_SERIAL = "serial" in mode
+            streams.DEBUG_DELAY_NS = 300_000 if "delay" in mode else args.delay_ns
+            streams.DEBUG_SERIAL = "serial" in mode
             g, w, spans = one_run(args, hog, runner=mode.startswith("runner"))
             res.append((mode, g, w))
         m0, g0, w0 = res[0]

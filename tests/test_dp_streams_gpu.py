@@ -44,6 +44,7 @@ def _steps(dp=None, n=4, mode="default"):
     import test_dp_capture_gpu as C
     import test_dp_ragged_gpu as R
     from espnet_amd import hip_ops
+    from espnet_amd._lib import lib
     from espnet_amd.train.trainer import Trainer
     _, m, opt, sched = C._setup(amp=True, dropout=0.1)
     if dp is not None:
@@ -56,6 +57,8 @@ def _steps(dp=None, n=4, mode="default"):
         return orig(*a, **k)
 
     opt.compute_grad_norm = snap
+    spin, spins = lib.ea_debug_spin, []
+    lib.ea_debug_spin = lambda *a: (spins.append(a), spin(*a))[1]
     prev = hip_ops.DEBUG_DELAY_NS, hip_ops.DEBUG_SERIAL
     hip_ops.DEBUG_DELAY_NS = 300_000 if mode == "delay" else 0
     hip_ops.DEBUG_SERIAL = mode == "serial"
@@ -65,6 +68,9 @@ def _steps(dp=None, n=4, mode="default"):
         torch.cuda.synchronize()
     finally:
         hip_ops.DEBUG_DELAY_NS, hip_ops.DEBUG_SERIAL = prev
+        lib.ea_debug_spin = spin
+    # the switch set above is the one the forks read: every segment spins, and only in that mode
+    assert len(spins) > 0 if mode == "delay" else len(spins) == 0, (mode, len(spins))
     return grads, m.arena.data.cpu().clone(), m
 
 

@@ -52,7 +52,7 @@ def test_scale_dropout_colsum_matches_two_pass(rows, cols, dt):
     y2 = torch.empty_like(y1)
     c1 = torch.ones(cols, device="cuda")
     c2 = torch.ones(cols, device="cuda")
-    w, wn = ops._ws(x.device)
+    w, wn = ops.f32_ws(x.device)
     lib.ea_scale_dropout_colsum(rows, cols, x.data_ptr(), cols, y1.data_ptr(), ops.dt(y1), cols, 0.5, 0.1, 1234,
                                 c1.data_ptr(), 1, w, wn, ops.stream())
     ops.scale_dropout(x, y2, scale=0.5, p=0.1, seed=1234)
