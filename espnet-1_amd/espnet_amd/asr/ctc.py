@@ -63,7 +63,8 @@ class CTC(nn.Module):
 
     def softmax(self, hs_pad):
         """ctc.py:99-107: softmax(ctc_lo(hs_pad), dim=2) -> (B, T, V).  An inference helper
-        here (no autograd; the interCTC conditioning that differentiates it is not built)."""
+        here (no autograd): the self-conditioned CTC taps, which differentiate it, run their own
+        softmax inside the encoder (layers/interctc.py, ea_softmax_lse_rows)."""
         return self._softmax(hs_pad, False)
 
     def log_softmax(self, hs_pad):

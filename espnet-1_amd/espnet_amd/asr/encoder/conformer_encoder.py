@@ -1,10 +1,12 @@
 """ConformerEncoder — drop-in for espnet2/asr/encoder/conformer_encoder.py:49-377.
 
 Same constructor signature, option validation and state_dict layout; forward runs the
-HIP path: Conv2dSubsampling (SubsampleFn) -> N x ConformerBlockFn -> after_norm.
+HIP path: Conv2dSubsampling (SubsampleFn) -> N x ConformerBlockFn -> after_norm, with an
+InterCTCTapFn (layers/interctc.py) behind every layer in interctc_layer_idx.
 Only the configuration the reference's ASR recipes train (input_layer conv2d,
-rel_pos_type latest, rel_pos / rel_selfattn, macaron, conv module, normalize_before) is
-implemented; other choices raise NotImplementedError instead of silently diverging.
+rel_pos_type latest, rel_pos / rel_selfattn, macaron, conv module, normalize_before,
+intermediate / self-conditioned CTC) is implemented; other choices raise NotImplementedError
+instead of silently diverging.
 """
 from __future__ import annotations
 
@@ -16,6 +18,7 @@ from torch import nn
 from ...layers.common import LayerNormFn, multisequential_draw, site_seed
 from ...layers.conformer import (ConvolutionModule, EncoderLayer, LayerNorm,
                                  PositionwiseFeedForward, RelPositionMultiHeadedAttention)
+from ...layers.interctc import InterCTCTapFn, TapState
 from ...layers.subsampling import Conv2dSubsampling, RelPositionalEncoding
 from ... import hip_ops as ops
 from ..._lib import lib
@@ -36,6 +39,17 @@ class AbsEncoder(nn.Module):
 
 
 class _AfterNorm(nn.LayerNorm):
+    def bind(self, arena, prefix, cd):
+        from ...layers.common import Bound
+        self._b = Bound(arena, prefix, cd)
+
+
+class ConditioningLayer(nn.Linear):
+    """Linear(vocab_size, output_size) of self-conditioned CTC (espnet_model.py:105-108):
+    x + conditioning_layer(softmax(ctc_lo(after_norm(x)))) at every tap; run by InterCTCTapFn."""
+
+    _b = None
+
     def bind(self, arena, prefix, cd):
         from ...layers.common import Bound
         self._b = Bound(arena, prefix, cd)
@@ -101,8 +115,8 @@ class ConformerEncoder(AbsEncoder):
             unsupported.append(f"positionwise_layer_type={positionwise_layer_type}")
         if activation_type != "swish":
             unsupported.append(f"activation_type={activation_type}")
-        if interctc_layer_idx or stochastic_depth_rate not in (0, 0.0) or layer_drop_rate > 0:
-            unsupported.append("interctc/stochastic depth/layer drop")
+        if stochastic_depth_rate not in (0, 0.0) or layer_drop_rate > 0:
+            unsupported.append("stochastic depth/layer drop")
         if not normalize_before or concat_after or not use_cnn_module:
             unsupported.append("normalize_before=False/concat_after/use_cnn_module=False")
         if unsupported:
@@ -127,8 +141,11 @@ class ConformerEncoder(AbsEncoder):
         self.encoders = nn.Sequential(*layers)
         self.after_norm = _AfterNorm(output_size, eps=1e-12)
         self.interctc_layer_idx = interctc_layer_idx
+        if len(interctc_layer_idx) > 0:  # conformer_encoder.py:292-293
+            assert 0 < min(interctc_layer_idx) and max(interctc_layer_idx) < num_blocks
         self.interctc_use_conditioning = interctc_use_conditioning
-        self.conditioning_layer = None
+        self.conditioning_layer = None  # ESPnetASRModel creates it (a ConditioningLayer), as the reference does
+        self._taps = TapState()
 
     def output_size(self) -> int:
         return self._output_size
@@ -145,11 +162,20 @@ class ConformerEncoder(AbsEncoder):
         for i, layer in enumerate(self.encoders):
             layer.bind(arena, f"{prefix}encoders.{i}.", cd)
         self.after_norm.bind(arena, prefix + "after_norm.", cd)
+        if self.conditioning_layer is not None:
+            self.conditioning_layer.bind(arena, prefix + "conditioning_layer.", cd)
         self._cd = cd
 
     def forward(self, xs_pad: torch.Tensor, ilens: torch.Tensor, prev_states=None, ctc=None,
-                seed: int = 0) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
-        """conformer_encoder.py:300-377.  xs_pad (B,T,F) f32 on the GPU, ilens (B,) int64."""
+                seed: int = 0, interctc_targets=None) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
+        """conformer_encoder.py:300-377.  xs_pad (B,T,F) f32 on the GPU, ilens (B,) int64.
+
+        With interctc_layer_idx the first result is (x, [(layer, y_layer), ...]) like the
+        reference's, the y the taps' after_norm outputs.  `ctc`: the model's CTC head — the taps
+        run its projection here (layers/interctc.py), for the conditioning and, given
+        `interctc_targets` = (text (B, Lmax) padded with -1, text_lengths), for their losses,
+        left in `self.interctc_losses` as [(layer, loss)] (espnet_model.py:242-286 computes them
+        from the returned y; here the loss shares the tap's logits with the conditioning)."""
         B, T, _ = xs_pad.shape
         if T < 7:  # check_short_utt, subsampling.py:31-43
             raise TooShortUttError(f"has {T} frames and is too short for subsampling "
@@ -158,10 +184,42 @@ class ConformerEncoder(AbsEncoder):
         olens = torch.empty(B, dtype=torch.long, device=xs_pad.device)
         lib.ea_subsample_lens(B, T, ilens.data_ptr(), olens.data_ptr(), ops.stream())
         x = self.embed(xs_pad, seed)
-        multisequential_draw(len(self.encoders))
+        taps = self.interctc_layer_idx
+        if not taps:
+            multisequential_draw(len(self.encoders))
+        # (with taps the reference loops over the layers itself, conformer_encoder.py:345: no
+        # MultiSequential.forward, so no layer-drop draw from the host generator)
         T2 = x.shape[1]
         pos = self.embed.out[1].pos_emb(T2, x.device, self._cd, self.training, site_seed(seed, 0, 9))
-        for layer in self.encoders:
+        if not taps:
+            for layer in self.encoders:
+                x = layer(x, pos, olens, seed)
+            x = LayerNormFn.apply(x, self.after_norm)
+            return x, olens, None
+        if ctc is None and self.interctc_use_conditioning:
+            raise ValueError("interctc_use_conditioning needs the CTC head: encoder(..., ctc=model.ctc)")
+        ys = ylens = None
+        Lmax = 0
+        if interctc_targets is not None and ctc is not None:
+            ys, ylens = interctc_targets
+            ys = ys.contiguous()
+            Lmax = int(ys.shape[1])
+        # the taps and the final after_norm / CTC head write the same gradients: the lowest tap
+        # reports them ready (TapState), when this forward builds a graph through the taps
+        in_graph = ctc is not None and torch.is_grad_enabled() and x.requires_grad and (
+            self.interctc_use_conditioning or ys is not None)
+        self._taps.arm(in_graph, self.after_norm, ctc)
+        intermediate_outs, losses = [], []
+        for li, layer in enumerate(self.encoders):
             x = layer(x, pos, olens, seed)
+            if li + 1 in taps:
+                if ctc is None:
+                    intermediate_outs.append((li + 1, LayerNormFn.apply(x, self.after_norm)))
+                    continue
+                x, loss_ic, y = InterCTCTapFn.apply(x, olens, ys, ylens, self, ctc, Lmax, not intermediate_outs)
+                intermediate_outs.append((li + 1, y))
+                if ys is not None:
+                    losses.append((li + 1, loss_ic))
+        self.interctc_losses = losses
         x = LayerNormFn.apply(x, self.after_norm)
-        return x, olens, None
+        return (x, intermediate_outs), olens, None

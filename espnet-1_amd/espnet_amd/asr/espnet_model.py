@@ -19,6 +19,7 @@ from .. import hip_ops as ops
 from .._lib import lib
 from ..arena import ParamArena
 from ..layers.common import site_seed
+from ..layers.interctc import InterCTCMixFn
 from ..layers.losses import CombineFn, LabelSmoothingLossFn
 from .ctc import CTC
 from .error_calculator import ErrorCalculator
@@ -101,8 +102,17 @@ class ESPnetASRModel(AbsESPnetModel):
         super().__init__()
         if preencoder is not None or postencoder is not None:
             raise NotImplementedError("preencoder/postencoder are outside the HIP hot path (SURVEY.md §2a)")
-        if joint_network is not None or interctc_weight != 0.0 or lang_token_id != -1:
-            raise NotImplementedError("transducer / interCTC / lang token are not on the path")
+        if joint_network is not None or lang_token_id != -1:
+            raise NotImplementedError("transducer / lang token are not on the path")
+        taps = list(getattr(encoder, "interctc_layer_idx", None) or [])
+        if taps and aux_ctc:
+            raise NotImplementedError("aux_ctc with intermediate CTC: a tap's loss shares its logits with the "
+                                      "conditioning and takes the step's text (no auxiliary targets)")
+        if taps and ctc is not None and ctc.dropout_rate > 0:
+            raise NotImplementedError("ctc_conf dropout_rate > 0 with intermediate CTC: a tap computes ctc_lo once for "
+                                      "its loss and its conditioning, and the reference drops out the loss branch only")
+        if taps and (ctc is None or ctc_weight == 0.0):
+            raise NotImplementedError("intermediate CTC needs the CTC head (ctc_weight > 0)")
         self.blank_id = token_list.index(sym_blank) if sym_blank in token_list else 0
         self.sos = token_list.index(sym_sos) if sym_sos in token_list else vocab_size - 1
         self.eos = token_list.index(sym_eos) if sym_eos in token_list else vocab_size - 1
@@ -120,7 +130,11 @@ class ESPnetASRModel(AbsESPnetModel):
         self.preencoder = None
         self.postencoder = None
         self.encoder = encoder
-        self.encoder.interctc_use_conditioning = False
+        if not hasattr(self.encoder, "interctc_use_conditioning"):  # espnet_model.py:103-108
+            self.encoder.interctc_use_conditioning = False
+        if self.encoder.interctc_use_conditioning:
+            from .encoder.conformer_encoder import ConditioningLayer
+            self.encoder.conditioning_layer = ConditioningLayer(vocab_size, self.encoder.output_size())
         self.use_transducer_decoder = False
         self.error_calculator = None
         if ctc_weight < 1.0:
@@ -256,9 +270,16 @@ class ESPnetASRModel(AbsESPnetModel):
         if self.ignore_id != -1:
             text = text.masked_fill(text == -1, self.ignore_id)
         text_lengths = self._dev(text_lengths, torch.long)
+        # intermediate CTC: the taps compute their losses inside the encoder, from the logits
+        # their conditioning uses too (layers/interctc.py)
+        ic_targets = (text, text_lengths) if self.interctc_weight != 0.0 and self._has_taps() else None
         encoder_out, encoder_out_lens = self.encode(speech, speech_lengths, _seed=seed, _smax=sl_max,
-                                                    _lens_host=kwargs.get("_lens_host"))
+                                                    _lens_host=kwargs.get("_lens_host"), _interctc_targets=ic_targets)
+        intermediate_outs = None
+        if isinstance(encoder_out, tuple):
+            encoder_out, intermediate_outs = encoder_out
         self._last_encoder_out = (encoder_out, encoder_out_lens)
+        self._last_intermediate_outs = intermediate_outs
         stats = dict()
         loss_ctc = loss_att = acc_att = None
         if self.ctc_weight != 0.0:
@@ -269,6 +290,16 @@ class ESPnetASRModel(AbsESPnetModel):
             if not self.training and self.error_calculator is not None:  # :571-575
                 ys_hat = self.ctc.argmax(encoder_out)
                 stats["cer_ctc"] = self.error_calculator(ys_hat.cpu(), text.cpu(), is_ctc=True)
+        if ic_targets is not None and intermediate_outs is not None:  # espnet_model.py:242-286
+            losses = self.encoder.interctc_losses
+            for (layer_idx, loss_ic), (_, y) in zip(losses, intermediate_outs):
+                stats[f"loss_interctc_layer{layer_idx}"] = loss_ic.detach()
+                cer_ic = None
+                if not self.training and self.error_calculator is not None:
+                    cer_ic = self.error_calculator(self.ctc.argmax(y).cpu(), text.cpu(), is_ctc=True)
+                stats[f"cer_interctc_layer{layer_idx}"] = cer_ic
+        else:
+            losses = None
         if self.ctc_weight != 1.0:
             loss_att, acc_att = self._calc_att_loss(encoder_out, encoder_out_lens, text, text_lengths,
                                                     seed=site_seed(seed, 600, 1))
@@ -284,6 +315,10 @@ class ESPnetASRModel(AbsESPnetModel):
             stats["cer"] = None
             stats["wer"] = None
         ops.join_aux()  # the CTC lattice ran on the auxiliary stream beside the decoder
+        if losses:
+            # loss_ctc = (1-w)*loss_ctc + w*mean(tap losses), espnet_model.py:281-286 (the taps'
+            # lattices ran on the auxiliary stream too; stats["loss_ctc"] is the unmixed loss)
+            loss_ctc = InterCTCMixFn.apply(float(self.interctc_weight), loss_ctc, *[l for _, l in losses])
         if self.ctc_weight == 0.0:
             loss = loss_att
         elif self.ctc_weight == 1.0:
@@ -312,10 +347,14 @@ class ESPnetASRModel(AbsESPnetModel):
             return self.frontend(speech, lens)
         return speech, lens
 
-    def encode(self, speech, speech_lengths, _seed=None, _smax=None, _lens_host=None):
+    def _has_taps(self) -> bool:
+        return bool(getattr(self.encoder, "interctc_layer_idx", None))
+
+    def encode(self, speech, speech_lengths, _seed=None, _smax=None, _lens_host=None, _interctc_targets=None):
         """espnet_model.py:351-412 (feats -> specaug (training) -> normalize -> encoder).
         `_lens_host`: the lengths as host ints, when the caller has them (SpecAug's
-        equal-length test needs them on the host, time_warp.py:73)."""
+        equal-length test needs them on the host, time_warp.py:73).  An encoder with
+        intermediate-CTC taps returns ((encoder_out, [(layer, y), ...]), lens), as the reference's."""
         seed = self._next_seed() if _seed is None else _seed
         if self.specaug is not None and self.training and _lens_host is None and speech_lengths.device.type == "cpu":
             _lens_host = [int(v) for v in speech_lengths.tolist()]
@@ -327,7 +366,11 @@ class ESPnetASRModel(AbsESPnetModel):
             feats, feats_lengths = self.specaug(feats, feats_lengths, lens_host=_lens_host)
         if self.normalize is not None:
             feats, feats_lengths = self.normalize(feats, feats_lengths)
-        encoder_out, encoder_out_lens, _ = self.encoder(feats, feats_lengths, seed=seed)
+        if self._has_taps():
+            encoder_out, encoder_out_lens, _ = self.encoder(feats, feats_lengths, ctc=self.ctc, seed=seed,
+                                                            interctc_targets=_interctc_targets)
+        else:
+            encoder_out, encoder_out_lens, _ = self.encoder(feats, feats_lengths, seed=seed)
         return encoder_out, encoder_out_lens
 
     def _att_argmax(self):

@@ -18,6 +18,16 @@ from typing import List, Tuple
 import torch
 
 
+def _encode(model, speech, speech_lengths):
+    """model.encode for the decoders: an encoder with intermediate-CTC taps returns
+    ((encoder_out, intermediate_outs), lens) (espnet_model.py:409-410); decoding uses
+    encoder_out, as asr_inference.py does."""
+    enc, olens = model.encode(speech, speech_lengths)
+    if isinstance(enc, tuple):
+        enc = enc[0]
+    return enc, olens
+
+
 def _collapse(ids, blank=0):
     out, prev = [], None
     for t in ids:
@@ -35,7 +45,7 @@ def ctc_greedy(model, speech: torch.Tensor, speech_lengths: torch.Tensor) -> Lis
         res = []
         for b in range(speech.shape[0]):
             le = int(speech_lengths[b])
-            enc, olens = model.encode(speech[b:b + 1, :le], speech_lengths[b:b + 1])
+            enc, olens = _encode(model, speech[b:b + 1, :le], speech_lengths[b:b + 1])
             ids = model.ctc.argmax(enc)[0, :int(olens[0])].tolist()
             res.append(_collapse(ids, model.blank_id))
         return res
@@ -55,7 +65,7 @@ def attention_greedy(model, speech: torch.Tensor, speech_lengths: torch.Tensor, 
         sos, eos = model.sos, model.eos
         for b in range(speech.shape[0]):
             le = int(speech_lengths[b])
-            enc, olens = model.encode(speech[b:b + 1, :le], speech_lengths[b:b + 1])
+            enc, olens = _encode(model, speech[b:b + 1, :le], speech_lengths[b:b + 1])
             T = enc.shape[1]
             if maxlenratio == 0:
                 maxlen = T
@@ -107,7 +117,7 @@ def attention_beam_search(model, speech: torch.Tensor, speech_lengths: torch.Ten
         res = []
         for b in range(speech.shape[0]):
             le = int(speech_lengths[b])
-            enc, _ = model.encode(speech[b:b + 1, :le], speech_lengths[b:b + 1])
+            enc, _ = _encode(model, speech[b:b + 1, :le], speech_lengths[b:b + 1])
             res.append(bs(enc[0], maxlenratio=maxlenratio, minlenratio=minlenratio))
         return res
     finally:

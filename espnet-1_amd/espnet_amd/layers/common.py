@@ -172,6 +172,16 @@ def site_dv(dx, dv, bias_g, scale, p, seed, cd):
     return dv
 
 
+def shared_grad_ready(module):
+    """ops.grad_ready of a node whose parameters the encoder's intermediate-CTC taps also write
+    (after_norm, the CTC head).  With taps in the graph the node is not their last writer: the
+    encoder marks the module (layers/interctc.py TapState) and the lowest tap's backward, the
+    last of them, reports instead — an early report would let the data-parallel hook all-reduce
+    a bucket that is written again afterwards."""
+    if not getattr(module, "_ready_deferred", False):
+        ops.grad_ready(module._b)
+
+
 class LayerNormFn(torch.autograd.Function):
     """LayerNorm (eps 1e-12) on the f32 residual stream -> f32 (after_norm)."""
 
@@ -190,7 +200,7 @@ class LayerNormFn(torch.autograd.Function):
         dy2 = dy.reshape(-1, x2.shape[-1]).contiguous()
         dx = torch.empty_like(x2)
         ln_bwd(dy2, x2, module._b, "", mu, rs, dx, accumulate=False)
-        ops.grad_ready(module._b)
+        shared_grad_ready(module)
         return dx.view(dy.shape), None
 
 

@@ -8,7 +8,7 @@ import contextlib
 
 import torch
 
-from .common import F32, empty, lib, ops
+from .common import F32, empty, lib, ops, shared_grad_ready
 
 
 def _g(t):
@@ -112,7 +112,7 @@ class CTCFn(torch.autograd.Function):
             lib.ea_scale_by_scalar(dh.numel(), dh.data_ptr(), gl.data_ptr(), 1.0, st)
             lib.ea_axpy_dev(dW.numel(), dW.data_ptr(), b.g("ctc_lo.weight").data_ptr(), gl.data_ptr(), 1.0, st)
             lib.ea_axpy_dev(V, db.data_ptr(), b.g("ctc_lo.bias").data_ptr(), gl.data_ptr(), 1.0, st)
-            ops.grad_ready(b)
+            shared_grad_ready(ctc)
             return dh.view(B, T, d), None, None, None, None, None
         h, logits, lse, alpha, beta, nll, hlens, ys, ylens = ctx.save
         ctx.save = None
@@ -143,7 +143,7 @@ class CTCFn(torch.autograd.Function):
         if fork is not None:
             ops.join_aux()
             dh.record_stream(torch.cuda.current_stream())  # consumed on the main stream
-        ops.grad_ready(b)
+        shared_grad_ready(ctc)
         return dh.view(B, T, d), None, None, None, None, None
 
 

@@ -188,7 +188,9 @@ class CapturedTrainStep:
                 F = m.frontend.output_size()
                 lens_host = [int(m.frontend.stft.frames_lens(int(v))) for v in lens_host]
             m.specaug.predraw(B, T, F, lens_host, m._device)
-        layerdrop_draw(len(m.encoder.encoders))
+        if not getattr(m.encoder, "interctc_layer_idx", None):
+            # (an encoder with intermediate-CTC taps loops over its layers itself and draws nothing)
+            layerdrop_draw(len(m.encoder.encoders))
         if m.decoder is not None:
             layerdrop_draw(len(m.decoder.decoders))
 

@@ -577,6 +577,35 @@ int ea_ctc_loss_bwd(int B, int T, int V, const float* logits, long ldt, const lo
                     const float* gscale, float coef, void* grad, int grad_dtype, long ldg,
                     void* stream);
 
+/* Intermediate / self-conditioned CTC (conformer_encoder.py:341-367, espnet_model.py:242-286):
+ * a tap's differentiable vocabulary softmax.  lse[r] = the log-sum-exp of logits row r — the
+ * value ea_ctc_loss_fwd writes, bit for bit — and probs[r][v] = exp(x - lse) in probs_dtype
+ * (EA_F32 / EA_BF16, rows ldp apart).  One read of each row (kept in LDS for V <= 12288, else
+ * re-read through L2); any ld >= V, V <= 16384 and row alignment (16-B accesses where the row
+ * bases allow, element-wise otherwise).  Deterministic. */
+int ea_softmax_lse_rows(long rows, int V, const float* logits, long ld, float* lse, void* probs,
+                        int probs_dtype, long ldp, void* stream);
+
+/* ea_ctc_loss_fwd with the rows' log-sum-exp given (from ea_softmax_lse_rows) instead of
+ * computed: the lattice and loss = sum / B only. */
+int ea_ctc_loss_fwd_lse(int B, int T, int V, const float* logits, long ldt, const long long* hlens,
+                        const long long* ys, long ldys, const long long* ylens, int Lmax,
+                        const float* lse, double* alpha, double* beta, double* nll, float* loss_utt,
+                        float* loss, void* stream);
+
+/* Backward of a tap w.r.t. its logits, the CTC loss and the conditioning branch in one pass:
+ *   grad[r][v] = gscale[0]*coef*(p_v - occupancy_v)  (0 past hlens or if infeasible)
+ *              + p_v*(dp[r][v] - sum_u p_u*dp[r][u]),      p = exp(logits - lse)
+ * dp (the gradient w.r.t. the tap's probs, rows lddp apart) and grad in grad_dtype.  The first
+ * term is ea_ctc_loss_bwd's: with dp all zero the output equals that entry point's.  dp NULL:
+ * the first term only; alpha NULL (a tap without a loss; hlens .. gscale unused): the second
+ * only.  Any ld >= V, V <= 16384 and row alignment, as above.  No atomics: deterministic. */
+int ea_interctc_dlogits(int B, int T, int V, const float* logits, long ldt, const long long* hlens,
+                        const long long* ys, long ldys, const long long* ylens, int Lmax,
+                        const float* lse, const double* alpha, const double* beta, const double* nll,
+                        const float* gscale, float coef, const void* dp, long lddp, void* grad,
+                        int grad_dtype, long ldg, void* stream);
+
 /* LabelSmoothingLoss + th_accuracy (label_smoothing_loss.py:41-63, nets_utils.py:304-324):
  * loss[0], acc[0] (correct/valid tokens), inv_denom[0] = 1/(#tokens or batch). */
 int ea_lsm_loss_fwd(long rows, int V, const float* x, long ldx, const long long* tgt, float smoothing,
