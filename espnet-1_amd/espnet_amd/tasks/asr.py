@@ -23,6 +23,7 @@ from ..asr.abs_modules import AbsFrontend, AbsNormalize, AbsSpecAug
 from ..asr.ctc import CTC
 from ..asr.decoder.transformer_decoder import AbsDecoder, TransformerDecoder
 from ..asr.encoder.conformer_encoder import AbsEncoder, ConformerEncoder
+from ..asr.encoder.e_branchformer_encoder import EBranchformerEncoder
 from ..asr.encoder.transformer_encoder import TransformerEncoder
 from ..asr.espnet_model import AbsESPnetModel, ESPnetASRModel, UtteranceMVN
 from ..asr.frontend.default import DefaultFrontend, GlobalMVN
@@ -39,7 +40,8 @@ specaug_choices = ClassChoices("specaug", dict(specaug=SpecAug), type_check=AbsS
 normalize_choices = ClassChoices("normalize", dict(global_mvn=GlobalMVN, utterance_mvn=UtteranceMVN),
                                  type_check=AbsNormalize, default="utterance_mvn", optional=True)
 model_choices = ClassChoices("model", dict(espnet=ESPnetASRModel), type_check=AbsESPnetModel, default="espnet")
-encoder_choices = ClassChoices("encoder", dict(conformer=ConformerEncoder, transformer=TransformerEncoder),
+encoder_choices = ClassChoices("encoder", dict(conformer=ConformerEncoder, transformer=TransformerEncoder,
+                                               e_branchformer=EBranchformerEncoder),
                                type_check=AbsEncoder, default="rnn")
 decoder_choices = ClassChoices("decoder", dict(transformer=TransformerDecoder), type_check=AbsDecoder, default=None,
                                optional=True)

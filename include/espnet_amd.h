@@ -738,6 +738,49 @@ int ea_beam_select(int n, int V, int P, int beam, int T, const float* logp, long
                    float w_ctc, const float* r_new, int* rec_i, float* rec_f, int* last_next,
                    unsigned long long* rptr_next, float* prefix_next, float* score_next, void* stream);
 
+/* ---- E-Branchformer block (espnet2/asr/layers/cgmlp.py, e_branchformer_encoder.py:148-164).
+ * All activations are channel-last rows in the compute dtype `dtype` (EA_F32 / EA_BF16),
+ * densely packed and 16-B aligned; K in {3, 5, 7, 15, 31}; U % 8 == 0; parameters and their
+ * gradients f32.  h (B*T, U) is channel_proj1's PRE-activation (Linear + bias, cgmlp.py:98): the
+ * exact erf GELU is applied inside these kernels and the activated copy is never stored.
+ * C = U / 2: columns [0, C) of h are x_r, columns [C, U) the gate x_g (cgmlp.py:68).
+ *
+ * ea_csgu_stats: per row, mean and rstd = 1 / sqrt(var + eps) (biased variance) of
+ * gelu(h[row, C:]) — the statistics of the CSGU's LayerNorm(C) (cgmlp.py:70), f32. */
+int ea_csgu_stats(int rows, int U, const void* h, int dtype, float eps, float* mean, float* rstd, void* stream);
+/* ea_csgu_fwd (cgmlp.py:68-81, use_linear_after_conv=False, identity gate activation):
+ *   out[t, c] = dropout( gelu(h[t, c]) * ( bias[c] + sum_k w[c, k] * LN(gelu(h[t+k-P, C+c])) ) )
+ * P = (K-1)/2, frames outside [0, T) of the utterance contribute zero (Conv1d padding; the
+ * padding mask is not consulted, as in the reference); LN = (g - mean) * rstd * gamma + beta.
+ * out (B*T, C); dropout element index row * C + c of stream `seed` (none when p == 0). */
+int ea_csgu_fwd(int B, int T, int U, int K, const void* h, int dtype, const float* mean, const float* rstd,
+                const float* gamma, const float* beta, const float* w, const float* bias, float p,
+                unsigned long long seed, void* out, void* stream);
+/* ea_csgu_bwd: from dout (B*T, C), h and the row statistics (the normalised gate and the conv
+ * output are recomputed) writes dh (B*T, U) = [dx_r | dx_g] * gelu'(h), ready for channel_proj1's
+ * backward GEMMs, and (+)= dgamma, dbeta (C, the LayerNorm's), dw (C, K), dbias (C).  dln:
+ * (B*T) * C f32 scratch (the gradient of the normalised gate, handed from the tap pass to the
+ * LayerNorm row pass); workspace: per-block partials of the four parameter gradients, summed
+ * in fixed order (no atomics).  ea_csgu_bwd_ws_elems gives both sizes in elements. */
+int ea_csgu_bwd_ws_elems(int B, int T, int U, int K, long* dln_elems, long* ws_elems);
+int ea_csgu_bwd(int B, int T, int U, int K, const void* dout, const void* h, int dtype, const float* mean,
+                const float* rstd, const float* gamma, const float* beta, const float* w, const float* bias,
+                float p, unsigned long long seed, void* dh, float* dgamma, float* dbeta, float* dw, float* dbias,
+                int accumulate_params, float* dln, float* workspace, long ws_elems, void* stream);
+/* Merge convolution (e_branchformer_encoder.py:160-164): m = xc + bias + dwconv_K(xc) over the
+ * C = 2 * size channels of the concatenated branches, xc and m (B*T, C), C % 4 == 0.
+ * ea_merge_conv_bwd: dxc = dm + dwconv_K^T(dm), dw (C, K) and dbias (C) (+)= through per-block
+ * partials in workspace (ea_merge_conv_bwd_ws_elems).  With p > 0 the store also applies the
+ * two branch outputs' dropout masks (e_branchformer_encoder.py:146,157): columns [0, C/2)
+ * stream seed_a, columns [C/2, C) stream seed_b, element index row * (C/2) + column within the
+ * half — the law of a GEMM epilogue that wrote that half with N = C/2. */
+int ea_merge_conv_fwd(int B, int T, int C, int K, const void* xc, int dtype, const float* w, const float* bias,
+                      void* m, void* stream);
+int ea_merge_conv_bwd_ws_elems(int B, int T, int C, int K, long* ws_elems);
+int ea_merge_conv_bwd(int B, int T, int C, int K, const void* xc, const void* dm, int dtype, const float* w,
+                      float p, unsigned long long seed_a, unsigned long long seed_b, void* dxc, float* dw,
+                      float* dbias, int accumulate_params, float* workspace, long ws_elems, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
