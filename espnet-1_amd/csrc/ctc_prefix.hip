@@ -49,8 +49,11 @@ __global__ __launch_bounds__(256) void ctc_softmax_rows_kernel(int V, const floa
     if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
     __syncthreads();
   }
-  const float lz = m + logf(red[0]);
-  for (int v = threadIdx.x; v < V; v += 256) out[(long)t * V + v] = LOG ? row[v] - lz : expf(row[v] - lz);
+  // (x - m) - log(sum), as torch's log_softmax: m + log(sum) as one number would be rounded at the
+  // size of m (4e-6 on a log-prob for logits near 80); the softmax divides instead of exp(x - lz)
+  const float ls = logf(red[0]), inv = 1.f / red[0];
+  for (int v = threadIdx.x; v < V; v += 256)
+    out[(long)t * V + v] = LOG ? (row[v] - m) - ls : expf(row[v] - m) * inv;
 }
 
 __global__ void ctc_prefix_init_kernel(int T, int V, int blank, const float* __restrict__ logp, float* __restrict__ r0) {

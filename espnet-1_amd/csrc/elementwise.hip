@@ -909,6 +909,7 @@ __global__ void embed_fwd_kernel(long rows, int d, int L, const long long* __res
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     const long r = i / d;
     const int c = (int)(i % d);
+    // (contracted into one FMA: rounded once, where torch's x * xscale + pe rounds the product too)
     float v = E[tok[r] * d + c] * xscale + pe[(r % L) * d + c];
     if (p > 0.f) v *= drop_scale(seed, (uint64_t)i, p);
     y[i] = v;
@@ -1000,7 +1001,9 @@ __global__ void argmax_rows_kernel(long rows, int V, const float* __restrict__ x
   for (int o = 32; o > 0; o >>= 1) {
     const float ob = __shfl_xor(best, o, 64);
     const int oi = __shfl_xor(bi, o, 64);
-    if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+    // a NaN beats every number and the lowest NaN index wins among NaNs, as in the scan above
+    const bool on = ob != ob, bn = best != best;
+    if (on ? (!bn || oi < bi) : (!bn && (ob > best || (ob == best && oi < bi)))) { best = ob; bi = oi; }
   }
   if (lane == 0) out[r] = bi;
 }

@@ -490,7 +490,8 @@ int ea_embed_bwd(long rows, int d, const long long* tok, const float* dy, float 
 int ea_set_rng_salt(const unsigned long long* salt);
 int ea_rng_advance(unsigned long long* salt, void* stream);
 
-/* CTC.argmax (ctc.py:119-127): first maximal index per row (bit-exact alignment). */
+/* CTC.argmax (ctc.py:119-127): first maximal index per row (bit-exact alignment).  NaN follows
+ * torch.argmax: a NaN is greater than every number, and the first NaN of the row is returned. */
 int ea_argmax_rows(long rows, int V, const float* x, long ld, long long* out, void* stream);
 
 /* ---------------------------------------------------------------- attention */
@@ -504,7 +505,8 @@ int ea_attn_softmax_fwd(int B, int H, int T1, int T2, float scale, const float* 
                         long ldPd, void* stream);
 
 /* dS = scale * P*(dP - rowsum(P*dP)), dP = dropout_bwd(dPd); if dBD != NULL also
- * dBD[h][b][i][r] = dS[i, r-(T1-1-i)] (0 off the band) for r < 2*T1-1. */
+ * dBD[h][b][i][r] = dS[i, r-(T1-1-i)] (0 off the band) for r < 2*T1-1, in ds_dtype like dS.
+ * T2 <= 2048 (fwd and bwd): longer rows are EA_ERR_BAD_ARG and nothing is written. */
 int ea_attn_softmax_bwd(int B, int H, int T1, int T2, float scale, const float* dPd, long ldd,
                         const float* P, long ldP, float p, unsigned long long seed, void* dS,
                         int ds_dtype, long ldS, void* dBD, long ldBD, void* stream);
