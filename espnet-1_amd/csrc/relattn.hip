@@ -905,8 +905,13 @@ EA_DEV void km_dma8u(char* dst, int ir, const char* src, uint32_t ldb, int r0, i
 }
 
 // MM: dropout keep decisions — 0 none (p = 0), 1 the forward's bit mask, 2 the counter hash
-template <bool REL, int MM>
+// LEG (rel-pos only): the legacy score law, as in attn_fwd2_kernel (the shifted q+v image in the
+// ring's last 64 rows, free until chunk 0's prefetch).  The band gradient is still emitted with
+// the latest placement, dS[i,j] at row i, column T-1-i+j (ea_attn_legacy_band moves the columns
+// right of T one row down afterwards), so the in-kernel d(q+v) term (flags bit 0) is not offered.
+template <bool REL, int MM, bool LEG = false>
 __global__ __launch_bounds__(256, 2) void attn_bwdq2_kernel(AttnP a) {
+  static_assert(REL || !LEG, "the legacy law is a rel-pos law");
   using L = Q2<REL>;
   __shared__ __attribute__((aligned(16))) char sm[L::LDS];
   const int nqb = (a.T1 + QB - 1) / QB;
@@ -966,9 +971,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwdq2_kernel(AttnP a) {
   char* img_qv = sm + L::V + KC * 128;
   char* img_do = sm + L::WS;  // the per-wave areas: 4 x 5 KiB (rel-pos) or 4 x 2 KiB
   static_assert(NWAVE * L::WSZ >= QB * 128, "dO image fits the per-wave areas");
-  bf16x8 qa[2], qv[2], doa[2];
+  bf16x8 qa[2], qv[2], qv1[2], doa[2];
   {
+    char* img_qv1 = sm + L::P + 144 * 128;  // (LEG) ring rows [144, 208)
     const bf16* qsrc = a.q + (long)b * a.T1 * a.ldq + h * DK;
+    if (LEG) km_stage_bias(img_qv1, qsrc, a.ldq, i0 + 1, QB, a.T1, a.bv + h * DK, tid, 256);
     km_stage_out(img_qu, qsrc, a.ldq, i0, QB, a.T1, a.bu ? a.bu + h * DK : nullptr,
                  a.wsQu + (long)b * a.T1 * a.ldqu + h * DK, a.ldqu, tid, 256);
     if (REL)
@@ -1003,6 +1010,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwdq2_kernel(AttnP a) {
     for (int ks = 0; ks < 2; ++ks) {
       qa[ks] = km_frag(img_qu, 16 * w, ks, lane);
       if (REL) qv[ks] = km_frag(img_qv, 16 * w, ks, lane);
+      if (LEG) qv1[ks] = km_frag(img_qv1, 16 * w, ks, lane);
       doa[ks] = km_frag(img_do, 16 * w, ks, lane);
     }
   }
@@ -1092,7 +1100,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwdq2_kernel(AttnP a) {
     }
     if (REL) {
       // BDfull (16 x 80) over ring rows 64c + pb + [0, 80), gathered onto the diagonal
-      f32x4 bd[5];
+      const bool up_only = LEG && j0 > i0 + 16 * w + 15;
+      const bool mixed = LEG && !up_only && j0 + KC - 1 > i0 + 16 * w;
+      f32x4 bd[5], bd1[5];
       {
         bf16x8 pf[5][2];
         const int rb = (64 * c + pb) % RING;  // wave-uniform, a multiple of 16
@@ -1107,7 +1117,15 @@ __global__ __launch_bounds__(256, 2) void attn_bwdq2_kernel(AttnP a) {
         for (int t = 0; t < 5; ++t) {
           bd[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-          for (int ks = 0; ks < 2; ++ks) bd[t] = mfma(qv[ks], pf[t][ks], bd[t]);
+          for (int ks = 0; ks < 2; ++ks) bd[t] = mfma(LEG && up_only ? qv1[ks] : qv[ks], pf[t][ks], bd[t]);
+        }
+        if (LEG && mixed) {
+#pragma unroll
+          for (int t = 0; t < 5; ++t) {
+            bd1[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) bd1[t] = mfma(qv1[ks], pf[t][ks], bd1[t]);
+          }
         }
       }
       // (one bpermute per band tile and register: the two calls of neighbouring t are the same
@@ -1122,7 +1140,13 @@ __global__ __launch_bounds__(256, 2) void attn_bwdq2_kernel(AttnP a) {
         for (int t = 0; t < 4; ++t) {
           const float lo = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(bd[t][r])));
           const float hi = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(bd[t + 1][r])));
-          s[t][r] += sft >= 16 ? hi : lo;
+          float bv_ = sft >= 16 ? hi : lo;
+          if (LEG && mixed) {
+            const float lo1 = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(bd1[t][r])));
+            const float hi1 = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(bd1[t + 1][r])));
+            if (j0 + 16 * t + lc > ibase + r) bv_ = sft >= 16 ? hi1 : lo1;
+          }
+          s[t][r] += bv_;
         }
       }
     }
@@ -1300,6 +1324,15 @@ __global__ __launch_bounds__(256, 2) void attn_bwdq2_kernel(AttnP a) {
 // lane) instead of 16 two-byte stores, read back as the PV MFMA's A operand with transposed
 // reads.  Same arithmetic in the same order as attn_fwd_kernel: O, lse and the keep bits are
 // bit-identical.  MM: 0 no dropout, 1 dropout + keep bits to dmask, 2 dropout only.
+// LEG (rel-pos only): the legacy rel_shift (LegacyRelPositionMultiHeadedAttention, attention.py:
+// 114-206) against the extended table of ea_legacy_pext:
+//   score[i,j] += (q_{i + (j > i)} + v)·Pext[T-1-i+j]
+// the band law above with the query row one lower in the strict upper triangle.  A wave's 16
+// rows against a 64-key chunk: keys all at or left of the diagonal take the product of the q+v
+// rows as before; keys all right of it take the product of the rows shifted down by one (a
+// second q+v image of rows i0+1 .. i0+64, rows >= T1 zero, staged in the ring's third 64 rows,
+// which are free until chunk 0's prefetch); a chunk the diagonal crosses takes both products and
+// selects per element.  LEG = false compiles to the code it had before.
 template <bool REL>
 struct F2 {
   static constexpr int RINGF = 192;
@@ -1309,8 +1342,9 @@ struct F2 {
 };
 static_assert(F2<true>::LDS <= 80 * 1024, "two workgroups per CU");
 
-template <bool REL, int MM>
+template <bool REL, int MM, bool LEG = false>
 __global__ __launch_bounds__(256, 2) void attn_fwd2_kernel(AttnP a) {
+  static_assert(REL || !LEG, "the legacy law is a rel-pos law");
   using L = F2<REL>;
   constexpr int RF = L::RINGF;
   __shared__ __attribute__((aligned(16))) char sm[L::LDS];
@@ -1359,18 +1393,21 @@ __global__ __launch_bounds__(256, 2) void attn_fwd2_kernel(AttnP a) {
 #pragma unroll
   for (int ks = 0; ks < 2; ++ks) loff[ks] = lc * 128 + (((ks * 4 + g) ^ km_swz(lc)) << 4);
   // this wave's 16 query rows as A fragments (q + u, q + v), from images in the second buffers
-  bf16x8 qa[2], qv[2];
+  bf16x8 qa[2], qv[2], qv1[2];
   {
     char* img_qu = sm + L::K + KC * 128;
     char* img_qv = sm + L::V + KC * 128;
+    char* img_qv1 = sm + L::P + 2 * KC * 128;  // (LEG) ring rows [128, 192)
     const bf16* qsrc = a.q + (long)b * a.T1 * a.ldq + h * DK;
     km_stage_bias(img_qu, qsrc, a.ldq, i0, QB, a.T1, a.bu ? a.bu + h * DK : nullptr, tid, 256);
     if (REL) km_stage_bias(img_qv, qsrc, a.ldq, i0, QB, a.T1, a.bv + h * DK, tid, 256);
+    if (LEG) km_stage_bias(img_qv1, qsrc, a.ldq, i0 + 1, QB, a.T1, a.bv + h * DK, tid, 256);
     bar();
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
       qa[ks] = km_frag(img_qu, 16 * w, ks, lane);
       if (REL) qv[ks] = km_frag(img_qv, 16 * w, ks, lane);
+      if (LEG) qv1[ks] = km_frag(img_qv1, 16 * w, ks, lane);
     }
   }
   f32x4 oacc[4];
@@ -1418,7 +1455,11 @@ __global__ __launch_bounds__(256, 2) void attn_fwd2_kernel(AttnP a) {
     }
     if (REL) {
       // BDfull (16 x 80) over ring rows 64c + pb + [0, 80), gathered onto the diagonal
-      f32x4 bd[5];
+      // (LEG) this wave's rows i0 + 16w + [0, 16) against keys j0 + [0, 64): every key right of
+      // every row's diagonal -> the shifted rows alone; the diagonal inside -> both, selected below
+      const bool up_only = LEG && j0 > i0 + 16 * w + 15;
+      const bool mixed = LEG && !up_only && j0 + KC - 1 > i0 + 16 * w;
+      f32x4 bd[5], bd1[5];
       {
         bf16x8 pf[5][2];
         const int rb = (64 * c + pb) % RF;  // wave-uniform, a multiple of 16
@@ -1434,7 +1475,15 @@ __global__ __launch_bounds__(256, 2) void attn_fwd2_kernel(AttnP a) {
         for (int t = 0; t < 5; ++t) {
           bd[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-          for (int ks = 0; ks < 2; ++ks) bd[t] = mfma(qv[ks], pf[t][ks], bd[t]);
+          for (int ks = 0; ks < 2; ++ks) bd[t] = mfma(LEG && up_only ? qv1[ks] : qv[ks], pf[t][ks], bd[t]);
+        }
+        if (LEG && mixed) {
+#pragma unroll
+          for (int t = 0; t < 5; ++t) {
+            bd1[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) bd1[t] = mfma(qv1[ks], pf[t][ks], bd1[t]);
+          }
         }
       }
 #pragma unroll
@@ -1445,7 +1494,13 @@ __global__ __launch_bounds__(256, 2) void attn_fwd2_kernel(AttnP a) {
         for (int t = 0; t < 4; ++t) {
           const float lo = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(bd[t][r])));
           const float hi = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(bd[t + 1][r])));
-          s[t][r] += sft >= 16 ? hi : lo;
+          float v = sft >= 16 ? hi : lo;
+          if (LEG && mixed) {
+            const float lo1 = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(bd1[t][r])));
+            const float hi1 = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(bd1[t + 1][r])));
+            if (j0 + 16 * t + lc > ibase + r) v = sft >= 16 ? hi1 : lo1;
+          }
+          s[t][r] += v;
         }
       }
     }
@@ -1781,14 +1836,15 @@ __global__ __launch_bounds__(256, 2) void attn_bwdkv_kernel(AttnP a) {
 // costs one barrier; each wave computes the three BD tiles its 16 keys read and gathers them by
 // ds_bpermute (no shared BDfull image, no second barrier).  dK, dV stay in registers.
 constexpr int RINGK = 128;
-template <bool REL>
+template <bool REL, bool LEG = false>
 struct KV2 {
   static constexpr int IMG = BQ * 128;                          // one 32-row km image
   static constexpr int QU = 0, QV = QU + 2 * IMG, DO = QV + (REL ? 2 * IMG : 0), P = DO + 2 * IMG;
   static constexpr int SM = P + (REL ? RINGK * 128 : 0);        // [2][D 32 | L 32 | mask 2 x 32]
-  static constexpr int LDS = SM + 2 * 128 * 4;
+  static constexpr int QV1 = SM + 2 * 128 * 4;                  // (LEG) [2] q + v rows shifted down by one
+  static constexpr int LDS = QV1 + (LEG ? 2 * IMG : 0);
 };
-static_assert(KV2<true>::LDS <= 80 * 1024, "two workgroups per CU");
+static_assert(KV2<true, true>::LDS <= 80 * 1024, "two workgroups per CU");
 
 // km_frag_tr2 via asm (rows k0 + q for half 0, k1 + q for half 1)
 EA_DEV bf16x8 km_tr2_asm(const char* img, int k0, int k1, int n0, int lane) {
@@ -1804,9 +1860,14 @@ EA_DEV void dma_dword(char* lds, const void* src) {  // lane L writes lds + 4L
                                    (__attribute__((address_space(3))) void*)lds, 4, 0, 0);
 }
 
-template <bool REL, int MM>
+// LEG: the legacy score law — a 32-query tile against this wave's 16 keys takes the band product
+// of the q + v rows (keys at or left of every diagonal), of the rows shifted down by one (a second
+// image DMA'd from workspace rows i0 + 1 ..; keys right of every diagonal), or both with a select
+// per element.  dK and dV keep their form.
+template <bool REL, int MM, bool LEG = false>
 __global__ __launch_bounds__(256, 2) void attn_bwdkv2_kernel(AttnP a) {
-  using L = KV2<REL>;
+  static_assert(REL || !LEG, "the legacy law is a rel-pos law");
+  using L = KV2<REL, LEG>;
   __shared__ __attribute__((aligned(16))) char sm[L::LDS];
   const int nkb = (a.T2 + 63) / 64;
   const int z = blockIdx.x / nkb, kb = blockIdx.x % nkb;
@@ -1858,6 +1919,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwdkv2_kernel(AttnP a) {
       const int ir = 8 * w;
       km_dma8u(sm + L::QU + buf * L::IMG + ir * 128, ir, quh, ldqub, i0 + ir, a.T1, chx, lane);
       if (REL) km_dma8u(sm + L::QV + buf * L::IMG + ir * 128, ir, qvh, ldqvb, i0 + ir, a.T1, chx, lane);
+      // (row T1 is clamped to row T1 - 1, not zero: only keys j > T1 - 1 would read it)
+      if (LEG) km_dma8u(sm + L::QV1 + buf * L::IMG + ir * 128, ir, qvh, ldqvb, i0 + 1 + ir, a.T1, chx, lane);
       km_dma8u(sm + L::DO + buf * L::IMG + ir * 128, ir, doh, lddob, i0 + ir, a.T1, chx, lane);
       if (REL) {
         // first tile: all 96 rows (12 groups); later: the 32 new rows below the previous band
@@ -1912,13 +1975,19 @@ __global__ __launch_bounds__(256, 2) void attn_bwdkv2_kernel(AttnP a) {
       if (REL) {
         // BDfull tiles (mi, t) for t in {w, w+1, w+2}: band rows rs + 16t + [0, 16) with
         // rs = rs0 - 32m (ring position (16t - 32m) mod 128)
-        f32x4 bd[2][3];
+        const bool up_only = LEG && jw > i0 + BQ - 1;
+        const bool mixed = LEG && !up_only && jw + 15 > i0;
+        const char* qv1img = sm + L::QV1 + buf * L::IMG;
+        f32x4 bd[2][3], bd1[2][3];
         {
-          bf16x8 vq[2][2], pf[3][2];
+          bf16x8 vq[2][2], vq1[2][2], pf[3][2];
 #pragma unroll
           for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
-            for (int ks = 0; ks < 2; ++ks) vq[mi][ks] = ld128_asm(qvimg + 2048 * mi + loff[ks]);
+            for (int ks = 0; ks < 2; ++ks) {
+              vq[mi][ks] = ld128_asm((LEG && up_only ? qv1img : qvimg) + 2048 * mi + loff[ks]);
+              if (LEG && mixed) vq1[mi][ks] = ld128_asm(qv1img + 2048 * mi + loff[ks]);
+            }
 #pragma unroll
           for (int u = 0; u < 3; ++u) {
             const int rp = (((16 * (w + u) - 32 * m) % RINGK) + RINGK) % RINGK;
@@ -1933,6 +2002,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwdkv2_kernel(AttnP a) {
               bd[mi][u] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
               for (int ks = 0; ks < 2; ++ks) bd[mi][u] = mfma(vq[mi][ks], pf[u][ks], bd[mi][u]);
+              if (LEG && mixed) {
+                bd1[mi][u] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks) bd1[mi][u] = mfma(vq1[mi][ks], pf[u][ks], bd1[mi][u]);
+              }
             }
         }
         // (il = 16mi + 4g + r, jl = 16w + lc) reads BDfull column 31 - il + jl = 16(w + u) +
@@ -1947,7 +2021,14 @@ __global__ __launch_bounds__(256, 2) void attn_bwdkv2_kernel(AttnP a) {
             const float x1 = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(bd[mi][1][r])));
             const float x2 = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(bd[mi][2][r])));
             const int u = sft >> 4;
-            s[mi][r] += u == 0 ? x0 : (u == 1 ? x1 : x2);
+            float bv_ = u == 0 ? x0 : (u == 1 ? x1 : x2);
+            if (LEG && mixed) {
+              const float y0 = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(bd1[mi][0][r])));
+              const float y1 = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(bd1[mi][1][r])));
+              const float y2 = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(bd1[mi][2][r])));
+              if (jw + lc > i0 + 16 * mi + 4 * g + r) bv_ = u == 0 ? y0 : (u == 1 ? y1 : y2);
+            }
+            s[mi][r] += bv_;
           }
       }
       // keep words of rows 16mi + 4g + r (this lane's bit bpos), D_i, lse_i
@@ -2031,6 +2112,30 @@ __global__ __launch_bounds__(256, 2) void attn_bwdkv2_kernel(AttnP a) {
   }
 }
 
+// The legacy band from the band the dQ pass emits with the latest placement (dS[i,j] at row i,
+// logical column k = T-1-i+j, physical column k + shift; rows written in full): columns k <= T-1
+// (j <= i) stay in their row, column T (j == i+1, the constant zero of Pext) is zero, columns
+// k >= T+1 (j >= i+2) move one row down (row 0 gets zeros).  16-B pieces: (T + shift) % 8 == 0, so
+// a piece lies on one side of column T, which is the first element of its piece.
+__global__ __launch_bounds__(256) void legacy_band_kernel(long nhb, int T, int shift, const bf16* __restrict__ in,
+                                                          bf16* __restrict__ out, long ld) {
+  const int npc = (int)(ld / 8), cT = (T + shift) / 8;
+  const long n = nhb * T * npc;
+  for (long e = blockIdx.x * 256L + threadIdx.x; e < n; e += gridDim.x * 256L) {
+    const int pc = (int)(e % npc);
+    const long row = e / npc;  // hb * T + r
+    const int r = (int)(row % T);
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+    if (pc < cT) {
+      v = *(const uint4*)(in + row * ld + 8 * pc);
+    } else if (r > 0) {
+      v = *(const uint4*)(in + (row - 1) * ld + 8 * pc);
+      if (pc == cT) v.x &= 0xffff0000u;  // column T
+    }
+    *(uint4*)(out + row * ld + 8 * pc) = v;
+  }
+}
+
 AttnP make_p(int B, int H, int T1, int T2, const void* q, long ldq, const void* k, long ldk, const void* v, long ldv,
              const float* bu, const float* bv, const void* pp, long ldp, const long long* klen, int causal, float scale,
              float p, unsigned long long seed) {
@@ -2044,12 +2149,15 @@ AttnP make_p(int B, int H, int T1, int T2, const void* q, long ldq, const void* 
 
 }  // namespace
 
-extern "C" int ea_attn_fused_fwd2(int B, int H, int T1, int T2, int dk, const void* q, long ldq, const void* k,
-                                  long ldk, const void* v, long ldv, const float* bu, const float* bv,
-                                  const void* pp, long ldp, const long long* klen, int causal, float scale, float p,
-                                  unsigned long long seed, void* o, long ldo, float* lse, unsigned* dmask, int ldm,
-                                  void* stream) {
+extern "C" int ea_attn_fused_fwd2_mode(int B, int H, int T1, int T2, int dk, const void* q, long ldq, const void* k,
+                                       long ldk, const void* v, long ldv, const float* bu, const float* bv,
+                                       const void* pp, long ldp, const long long* klen, int causal, float scale,
+                                       float p, unsigned long long seed, void* o, long ldo, float* lse,
+                                       unsigned* dmask, int ldm, int rel_mode, void* stream) {
   EA_ENTRY();
+  EA_CHECK_ARG(rel_mode == EA_REL_LATEST || rel_mode == EA_REL_LEGACY);
+  const bool leg = rel_mode == EA_REL_LEGACY;
+  EA_CHECK_ARG(!leg || (pp != nullptr && !causal));
   EA_CHECK_ARG(dk == DK && B >= 1 && H >= 1 && T1 >= 1 && T2 >= 1);
   EA_CHECK_ARG(!pp || (T1 == T2 && bv != nullptr));
   EA_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && (!pp || ldp % 8 == 0));
@@ -2066,7 +2174,12 @@ extern "C" int ea_attn_fused_fwd2(int B, int H, int T1, int T2, int dk, const vo
   const bool off32 = fits(T2, ldk) && fits(T2, ldv) && (!pp || fits(2L * T1, ldp));
   const bool v1 = (ev && ev[0] == '1') || !off32;
   const int mm = p > 0.f ? (dmask ? 1 : 2) : 0;
-  if (v1) {
+  if (leg) {  // the pipelined kernel only: the original forward has no legacy form
+    EA_CHECK_ARG(!v1);
+    if (mm == 0) hipLaunchKernelGGL((attn_fwd2_kernel<true, 0, true>), grid, dim3(256), 0, st, a);
+    else if (mm == 1) hipLaunchKernelGGL((attn_fwd2_kernel<true, 1, true>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((attn_fwd2_kernel<true, 2, true>), grid, dim3(256), 0, st, a);
+  } else if (v1) {
     if (pp) hipLaunchKernelGGL(attn_fwd_kernel<true>, grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL(attn_fwd_kernel<false>, grid, dim3(256), 0, st, a);
   } else if (pp) {
@@ -2082,6 +2195,15 @@ extern "C" int ea_attn_fused_fwd2(int B, int H, int T1, int T2, int dk, const vo
   return 0;
 }
 
+extern "C" int ea_attn_fused_fwd2(int B, int H, int T1, int T2, int dk, const void* q, long ldq, const void* k,
+                                  long ldk, const void* v, long ldv, const float* bu, const float* bv,
+                                  const void* pp, long ldp, const long long* klen, int causal, float scale, float p,
+                                  unsigned long long seed, void* o, long ldo, float* lse, unsigned* dmask, int ldm,
+                                  void* stream) {
+  return ea_attn_fused_fwd2_mode(B, H, T1, T2, dk, q, ldq, k, ldk, v, ldv, bu, bv, pp, ldp, klen, causal, scale, p,
+                                 seed, o, ldo, lse, dmask, ldm, EA_REL_LATEST, stream);
+}
+
 extern "C" int ea_attn_fused_fwd(int B, int H, int T1, int T2, int dk, const void* q, long ldq, const void* k,
                                  long ldk, const void* v, long ldv, const float* bu, const float* bv,
                                  const void* pp, long ldp, const long long* klen, int causal, float scale, float p,
@@ -2090,7 +2212,7 @@ extern "C" int ea_attn_fused_fwd(int B, int H, int T1, int T2, int dk, const voi
                             o, ldo, lse, nullptr, 0, stream);
 }
 
-static int attn_bwd_launch(AttnP& a, bool rel, bool v2, hipStream_t st) {
+static int attn_bwd_launch(AttnP& a, bool rel, bool v2, hipStream_t st, bool leg = false) {
   const int nqb = (a.T1 + QB - 1) / QB, nkb = (a.T2 + 63) / 64;
   // the pipelined dQ pass addresses K / V / positional rows with 32-bit byte offsets from each
   // head's base (__umul24(row, row bytes))
@@ -2103,7 +2225,15 @@ static int attn_bwd_launch(AttnP& a, bool rel, bool v2, hipStream_t st) {
   const int mm = a.p > 0.f ? (a.dmask ? 1 : 2) : 0;
   const char* ev = getenv("EA_ATTN_BWDKV_V1");  // A/B: the original dK/dV pass
   const bool kv1 = ev && ev[0] == '1';
-  if (rel) {
+  if (leg) {  // the pipelined passes only: the original ones have no legacy form
+    EA_CHECK_ARG(rel && v2 && kv32 && !kv1 && !(a.flags & 1) && !a.causal);
+    if (mm == 0) hipLaunchKernelGGL((attn_bwdq2_kernel<true, 0, true>), gq, dim3(256), 0, st, a);
+    else if (mm == 1) hipLaunchKernelGGL((attn_bwdq2_kernel<true, 1, true>), gq, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((attn_bwdq2_kernel<true, 2, true>), gq, dim3(256), 0, st, a);
+    if (mm == 0) hipLaunchKernelGGL((attn_bwdkv2_kernel<true, 0, true>), gkv, dim3(256), 0, st, a);
+    else if (mm == 1) hipLaunchKernelGGL((attn_bwdkv2_kernel<true, 1, true>), gkv, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((attn_bwdkv2_kernel<true, 2, true>), gkv, dim3(256), 0, st, a);
+  } else if (rel) {
     if (v2 && mm == 0) hipLaunchKernelGGL((attn_bwdq2_kernel<true, 0>), gq, dim3(256), 0, st, a);
     else if (v2 && mm == 1) hipLaunchKernelGGL((attn_bwdq2_kernel<true, 1>), gq, dim3(256), 0, st, a);
     else if (v2) hipLaunchKernelGGL((attn_bwdq2_kernel<true, 2>), gq, dim3(256), 0, st, a);
@@ -2142,14 +2272,19 @@ extern "C" int ea_attn_fused_bwd_ws_bytes(int B, int H, int T1, long* bytes) {
   return 0;
 }
 
-extern "C" int ea_attn_fused_bwd2(int B, int H, int T1, int T2, int dk, const void* q, long ldq, const void* k,
-                                  long ldk, const void* v, long ldv, const float* bu, const float* bv,
-                                  const void* pp, long ldp, const long long* klen, int causal, float scale, float p,
-                                  unsigned long long seed, const void* o, long ldo, const float* lse, const void* dO,
-                                  long lddo, void* dq, long lddq, void* dkout, long lddk, void* dvout, long lddv,
-                                  void* dbd, long lddbd, float* bias_part, long ldpart, void* qv_out, long ldqv,
-                                  const unsigned* dmask, int ldm, void* ws, long ws_bytes, int flags, void* stream) {
+extern "C" int ea_attn_fused_bwd2_mode(int B, int H, int T1, int T2, int dk, const void* q, long ldq, const void* k,
+                                       long ldk, const void* v, long ldv, const float* bu, const float* bv,
+                                       const void* pp, long ldp, const long long* klen, int causal, float scale,
+                                       float p, unsigned long long seed, const void* o, long ldo, const float* lse,
+                                       const void* dO, long lddo, void* dq, long lddq, void* dkout, long lddk,
+                                       void* dvout, long lddv, void* dbd, long lddbd, float* bias_part, long ldpart,
+                                       void* qv_out, long ldqv, const unsigned* dmask, int ldm, void* ws,
+                                       long ws_bytes, int flags, int rel_mode, void* stream) {
   EA_ENTRY();
+  EA_CHECK_ARG(rel_mode == EA_REL_LATEST || rel_mode == EA_REL_LEGACY);
+  const bool leg = rel_mode == EA_REL_LEGACY;
+  // legacy: the pipelined passes (flags bit 1), no in-kernel d(q+v) term (bit 0), no causal mask
+  EA_CHECK_ARG(!leg || (pp != nullptr && !causal && (flags & 3) == 2));
   EA_CHECK_ARG(dk == DK && B >= 1 && H >= 1 && T1 >= 1 && T2 >= 1);
   EA_CHECK_ARG(!pp || (T1 == T2 && bv != nullptr));
   EA_CHECK_ARG(flags >= 0 && flags <= 7 && !((flags & 2) && (flags & 4)));
@@ -2179,7 +2314,33 @@ extern "C" int ea_attn_fused_bwd2(int B, int H, int T1, int T2, int dk, const vo
   a.wsQu = (bf16*)((char*)ws + qu_off); a.ldqu = (long)H * DK;
   if (qv_out) { a.wsQv = (bf16*)qv_out; a.ldqvw = ldqv; }
   else { a.wsQv = (bf16*)((char*)ws + qv_off); a.ldqvw = (long)H * DK; }
-  return attn_bwd_launch(a, pp != nullptr, v2, (hipStream_t)stream);
+  return attn_bwd_launch(a, pp != nullptr, v2, (hipStream_t)stream, leg);
+}
+
+extern "C" int ea_attn_fused_bwd2(int B, int H, int T1, int T2, int dk, const void* q, long ldq, const void* k,
+                                  long ldk, const void* v, long ldv, const float* bu, const float* bv,
+                                  const void* pp, long ldp, const long long* klen, int causal, float scale, float p,
+                                  unsigned long long seed, const void* o, long ldo, const float* lse, const void* dO,
+                                  long lddo, void* dq, long lddq, void* dkout, long lddk, void* dvout, long lddv,
+                                  void* dbd, long lddbd, float* bias_part, long ldpart, void* qv_out, long ldqv,
+                                  const unsigned* dmask, int ldm, void* ws, long ws_bytes, int flags, void* stream) {
+  return ea_attn_fused_bwd2_mode(B, H, T1, T2, dk, q, ldq, k, ldk, v, ldv, bu, bv, pp, ldp, klen, causal, scale, p,
+                                 seed, o, ldo, lse, dO, lddo, dq, lddq, dkout, lddk, dvout, lddv, dbd, lddbd,
+                                 bias_part, ldpart, qv_out, ldqv, dmask, ldm, ws, ws_bytes, flags, EA_REL_LATEST,
+                                 stream);
+}
+
+extern "C" int ea_attn_legacy_band(long nhb, int T1, const void* dbd, void* out, long lddbd, void* stream) {
+  EA_ENTRY();
+  EA_CHECK_ARG(nhb >= 0 && T1 >= 1 && dbd != nullptr && out != nullptr && dbd != out);
+  EA_CHECK_ARG(lddbd >= ea_attn_dbd_ld(T1) && lddbd % 8 == 0 && (uintptr_t)dbd % 16 == 0 && (uintptr_t)out % 16 == 0);
+  if (nhb == 0) return 0;
+  const int shift = ea_attn_dbd_shift_dev(T1);
+  const dim3 grid(ea_grid_cap(ea_cdiv(nhb * T1 * (lddbd / 8), 256), 8192)), blk(256);
+  hipLaunchKernelGGL(legacy_band_kernel, grid, blk, 0, (hipStream_t)stream, nhb, T1, shift, (const bf16*)dbd,
+                     (bf16*)out, lddbd);
+  EA_LAUNCH_CHECK();
+  return 0;
 }
 
 extern "C" int ea_attn_dbd_layout(int T1, int* shift, long* lddbd) {

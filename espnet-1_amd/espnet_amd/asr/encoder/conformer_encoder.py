@@ -4,12 +4,13 @@ Same constructor signature, option validation and state_dict layout; forward run
 HIP path: Conv2dSubsampling (SubsampleFn) -> N x ConformerBlockFn -> after_norm, with an
 InterCTCTapFn (layers/interctc.py) behind every layer in interctc_layer_idx.
 Only the configuration the reference's ASR recipes train (input_layer conv2d,
-rel_pos_type latest, rel_pos / rel_selfattn, macaron, conv module, normalize_before,
-intermediate / self-conditioned CTC) is implemented; other choices raise NotImplementedError
+rel_pos_type latest or legacy, (legacy_)rel_pos / (legacy_)rel_selfattn, macaron, conv module,
+normalize_before, intermediate / self-conditioned CTC) is implemented; other choices raise NotImplementedError
 instead of silently diverging.
 """
 from __future__ import annotations
 
+import logging
 from typing import List, Optional, Tuple, Union
 
 import torch
@@ -19,7 +20,7 @@ from ...layers.common import LayerNormFn, multisequential_draw, site_seed
 from ...layers.conformer import (ConvolutionModule, EncoderLayer, LayerNorm,
                                  PositionwiseFeedForward, RelPositionMultiHeadedAttention)
 from ...layers.interctc import InterCTCTapFn, TapState
-from ...layers.subsampling import Conv2dSubsampling, RelPositionalEncoding
+from ...layers.subsampling import Conv2dSubsampling, LegacyRelPositionalEncoding, RelPositionalEncoding
 from ... import hip_ops as ops
 from ..._lib import lib
 
@@ -107,7 +108,20 @@ class ConformerEncoder(AbsEncoder):
                                "embed") and not isinstance(input_layer, nn.Module) and input_layer is not None:
             raise ValueError("unknown input_layer: " + str(input_layer))
         unsupported = []
-        if pos_enc_layer_type != "rel_pos" or selfattention_layer_type != "rel_selfattn":
+        # conformer_encoder.py:155-196: each rel-pos attention asserts its own positional encoding
+        if pos_enc_layer_type == "rel_pos":
+            assert selfattention_layer_type == "rel_selfattn"
+        elif pos_enc_layer_type == "legacy_rel_pos":
+            assert selfattention_layer_type == "legacy_rel_selfattn"
+            logging.warning("Using legacy_rel_pos and it will be deprecated in the future.")
+        if selfattention_layer_type == "rel_selfattn":
+            assert pos_enc_layer_type == "rel_pos"
+        elif selfattention_layer_type == "legacy_rel_selfattn":
+            assert pos_enc_layer_type == "legacy_rel_pos"
+            logging.warning("Using legacy_rel_selfattn and it will be deprecated in the future.")
+        legacy = selfattention_layer_type == "legacy_rel_selfattn"
+        if (pos_enc_layer_type, selfattention_layer_type) not in (("rel_pos", "rel_selfattn"),
+                                                                  ("legacy_rel_pos", "legacy_rel_selfattn")):
             unsupported.append(f"{pos_enc_layer_type}/{selfattention_layer_type}")
         if input_layer != "conv2d":
             unsupported.append(f"input_layer={input_layer}")
@@ -124,15 +138,16 @@ class ConformerEncoder(AbsEncoder):
                                       "configuration only; unsupported: " + ", ".join(unsupported))
         if output_size % 8:
             raise ValueError("output_size must be a multiple of 8 (16-B aligned MFMA operands)")
+        pos_enc_class = LegacyRelPositionalEncoding if legacy else RelPositionalEncoding
         self.embed = Conv2dSubsampling(input_size, output_size, dropout_rate,
-                                       RelPositionalEncoding(output_size, positional_dropout_rate,
-                                                             max_pos_emb_len))
+                                       pos_enc_class(output_size, positional_dropout_rate, max_pos_emb_len))
         self.normalize_before = normalize_before
         layers = []
         for lnum in range(num_blocks):
             layers.append(EncoderLayer(
                 output_size,
-                RelPositionMultiHeadedAttention(attention_heads, output_size, attention_dropout_rate, zero_triu),
+                RelPositionMultiHeadedAttention(attention_heads, output_size, attention_dropout_rate, zero_triu,
+                                                legacy=legacy),
                 PositionwiseFeedForward(output_size, linear_units, dropout_rate),
                 PositionwiseFeedForward(output_size, linear_units, dropout_rate) if macaron_style else None,
                 ConvolutionModule(output_size, cnn_module_kernel),

@@ -16,12 +16,13 @@ import torch
 from .. import hip_ops as ops
 from ..hip_ops import ptr
 from .._lib import (ACT_NONE, ACT_RELU, ACT_SWISH, EPI_ACT, EPI_DACT, EPI_RESID, EPI_STORE,
-                    lib)
+                    REL_LATEST, REL_LEGACY, lib)
 
 __all__ = ["Bound", "rup", "empty", "ops", "lib", "EPI_ACT", "EPI_DACT", "EPI_RESID",
            "EPI_STORE", "ACT_NONE", "ACT_RELU", "ACT_SWISH", "site_seed", "attn_fwd", "attn_bwd",
            "LayerNormFn", "ln_fwd", "ln_bwd", "math", "F32", "fused_attn_ok", "attn_dmask",
-           "attn_fused_bwd", "dv_buf", "drop_arg", "site_dv", "multisequential_draw"]
+           "attn_fused_bwd", "dv_buf", "drop_arg", "site_dv", "multisequential_draw", "REL_LATEST",
+           "REL_LEGACY"]
 
 F32 = torch.float32
 
@@ -66,16 +67,17 @@ def dbd_layout(T1: int):
 
 def attn_fused_bwd(*, B, H, T1, T2, q, ldq, k, ldk, v, ldv, bu, bv, pp, ldp, klen, causal, scale, p, seed,
                    O, ldo, lse, dO, lddo, dq, lddq, dk, lddk, dv, lddv, dbd=None, ldbd=0, part=None,
-                   ldpart=0, qv_out=None, ldqv=0, dmask=None, ldm=0, flags=0):
-    """ea_attn_fused_bwd2 with its workspace (D_i, q+u, q+v handed between the two passes),
+                   ldpart=0, qv_out=None, ldqv=0, dmask=None, ldm=0, flags=0, rel_mode=0):
+    """ea_attn_fused_bwd2_mode with its workspace (D_i, q+u, q+v handed between the two passes),
     a stream-ordered allocation freed behind the launches."""
     n = ctypes.c_long(0)
     lib.ea_attn_fused_bwd_ws_bytes(B, H, T1, ctypes.addressof(n))
     ws = torch.empty(n.value, dtype=torch.uint8, device=dO.device)
-    lib.ea_attn_fused_bwd2(B, H, T1, T2, 64, ptr(q), ldq, ptr(k), ldk, ptr(v), ldv, ptr(bu), ptr(bv), ptr(pp),
-                           ldp, ptr(klen), int(causal), float(scale), float(p), seed, ptr(O), ldo, ptr(lse),
-                           ptr(dO), lddo, ptr(dq), lddq, ptr(dk), lddk, ptr(dv), lddv, ptr(dbd), ldbd, ptr(part),
-                           ldpart, ptr(qv_out), ldqv, ptr(dmask), ldm, ws.data_ptr(), n.value, flags, ops.stream())
+    lib.ea_attn_fused_bwd2_mode(B, H, T1, T2, 64, ptr(q), ldq, ptr(k), ldk, ptr(v), ldv, ptr(bu), ptr(bv), ptr(pp),
+                                ldp, ptr(klen), int(causal), float(scale), float(p), seed, ptr(O), ldo, ptr(lse),
+                                ptr(dO), lddo, ptr(dq), lddq, ptr(dk), lddk, ptr(dv), lddv, ptr(dbd), ldbd,
+                                ptr(part), ldpart, ptr(qv_out), ldqv, ptr(dmask), ldm, ws.data_ptr(), n.value, flags,
+                                rel_mode, ops.stream())
 
 
 def multisequential_draw(n: int):
@@ -206,9 +208,10 @@ class LayerNormFn(torch.autograd.Function):
 
 # ----------------------------------------------------------------------------- attention core
 def attn_fwd(q, k, v, *, B, H, T1, T2, dk, ldq, ldk, ldv, klen, causal, scale, p, seed, cd,
-             bd=None, ldbd=0):
+             bd=None, ldbd=0, rel_mode=0):
     """softmax(scale*(q k^T [+ rel_shift(bd)]) masked) -> dropout -> @ v, all (b,h) at once.
-    q/k/v are row views (row strides ldq/ldk/ldv, head h at column h*dk).  Returns
+    q/k/v are row views (row strides ldq/ldk/ldv, head h at column h*dk).  rel_mode: REL_LATEST,
+    or REL_LEGACY (the legacy rel_shift, bd taken against ea_legacy_pext's table).  Returns
     O (B*T1, H*dk) cd, P (f32 softmax), Pd (dropout(P) in cd), ldT."""
     dev = q.device
     ldT = rup(T2, 8)
@@ -217,10 +220,10 @@ def attn_fwd(q, k, v, *, B, H, T1, T2, dk, ldq, ldk, ldv, klen, causal, scale, p
              batch=B, nh=H, sA=(T1 * ldq, dk), sB=(T2 * ldk, dk), sC=(H * T1 * ldT, T1 * ldT),
              splitk=False)
     Pd = empty(B * H * T1 * ldT, dtype=cd, device=dev)
-    lib.ea_attn_softmax_fwd(B, H, T1, T2, scale, S.data_ptr(), ldT,
-                            0 if bd is None else bd.data_ptr(), ldbd,
-                            0 if klen is None else klen.data_ptr(), int(causal), float(p),
-                            seed, S.data_ptr(), ldT, Pd.data_ptr(), ops.dt(Pd), ldT, ops.stream())
+    lib.ea_attn_softmax_fwd_mode(B, H, T1, T2, scale, S.data_ptr(), ldT,
+                                 0 if bd is None else bd.data_ptr(), ldbd,
+                                 0 if klen is None else klen.data_ptr(), int(causal), float(p),
+                                 seed, S.data_ptr(), ldT, Pd.data_ptr(), ops.dt(Pd), ldT, rel_mode, ops.stream())
     O = empty(B * T1, H * dk, dtype=cd, device=dev)
     ops.gemm(Pd, v, O, M=T1, N=dk, K=T2, a_kmajor=1, b_kmajor=0, lda=ldT, ldb=ldv, ldc=H * dk,
              batch=B, nh=H, sA=(H * T1 * ldT, T1 * ldT), sB=(T2 * ldv, dk), sC=(T1 * H * dk, dk),
@@ -229,7 +232,7 @@ def attn_fwd(q, k, v, *, B, H, T1, T2, dk, ldq, ldk, ldv, klen, causal, scale, p
 
 
 def attn_bwd(dO, q, k, v, P, Pd, ldT, *, B, H, T1, T2, dk, ldq, ldk, ldv, scale, p, seed, cd,
-             dq, lddq, dk_, lddk, dv, lddv, dbd=None, ldbd=0):
+             dq, lddq, dk_, lddk, dv, lddv, dbd=None, ldbd=0, rel_mode=0):
     """Backward of attn_fwd: writes dq (scaled scores grad . k), dk_, dv; optionally the
     rel-pos band gradient dbd [h][b][i][ldbd]."""
     dev = dO.device
@@ -239,9 +242,9 @@ def attn_bwd(dO, q, k, v, P, Pd, ldT, *, B, H, T1, T2, dk, ldq, ldk, ldv, scale,
              batch=B, nh=H, sA=(T1 * d, dk), sB=(T2 * ldv, dk), sC=(H * T1 * ldT, T1 * ldT),
              splitk=False)
     dS = empty(B * H * T1 * ldT, dtype=cd, device=dev)
-    lib.ea_attn_softmax_bwd(B, H, T1, T2, scale, dPd.data_ptr(), ldT, P.data_ptr(), ldT, float(p),
-                            seed, dS.data_ptr(), ops.dt(dS), ldT,
-                            0 if dbd is None else dbd.data_ptr(), ldbd, ops.stream())
+    lib.ea_attn_softmax_bwd_mode(B, H, T1, T2, scale, dPd.data_ptr(), ldT, P.data_ptr(), ldT, float(p),
+                                 seed, dS.data_ptr(), ops.dt(dS), ldT,
+                                 0 if dbd is None else dbd.data_ptr(), ldbd, rel_mode, ops.stream())
     zs = (H * T1 * ldT, T1 * ldT)
     ops.gemm(dS, k, dq, M=T1, N=dk, K=T2, a_kmajor=1, b_kmajor=0, lda=ldT, ldb=ldk, ldc=lddq,
              batch=B, nh=H, sA=zs, sB=(T2 * ldk, dk), sC=(T1 * lddq, dk), splitk=False)

@@ -20,7 +20,7 @@ from torch import nn
 
 from .common import (ACT_SWISH, EPI_ACT, EPI_DACT, EPI_RESID, EPI_STORE, F32, Bound, attn_bwd, attn_dmask, dbd_layout,
                      attn_fused_bwd, attn_fwd, empty, fused_attn_ok, lib, ln_bwd, ln_fwd, math, ops, rup,
-                     site_seed, dv_buf, drop_arg, site_dv)
+                     site_seed, dv_buf, drop_arg, site_dv, REL_LATEST, REL_LEGACY)
 
 
 # ----------------------------------------------------------------------------- holders
@@ -69,12 +69,15 @@ class MultiHeadedAttention(nn.Module):
 
 
 class RelPositionMultiHeadedAttention(MultiHeadedAttention):
-    """transformer/attention.py:209-235 parameter set (linear_pos, pos_bias_u/v)."""
+    """transformer/attention.py:209-235 parameter set (linear_pos, pos_bias_u/v).  `legacy`:
+    LegacyRelPositionMultiHeadedAttention (attention.py:114-206), the same parameters with the
+    legacy rel_shift over a T-row positional table (rel_mode REL_LEGACY of the block)."""
 
-    def __init__(self, n_head, n_feat, dropout_rate, zero_triu=False):
+    def __init__(self, n_head, n_feat, dropout_rate, zero_triu=False, legacy=False):
         super().__init__(n_head, n_feat, dropout_rate)
         if zero_triu:
             raise NotImplementedError("zero_triu=True is not on the ASR hot path")
+        self.rel_mode = REL_LEGACY if legacy else REL_LATEST
         self.linear_pos = nn.Linear(n_feat, n_feat, bias=False)
         self.pos_bias_u = nn.Parameter(torch.Tensor(self.h, self.d_k))
         self.pos_bias_v = nn.Parameter(torch.Tensor(self.h, self.d_k))
@@ -207,21 +210,39 @@ class ConformerBlockFn(torch.autograd.Function):
                             shape=(3 * d, d)), qkv,
                    epi=ops.make_epi(bias=b.f(A + "linear_q.bias", A + "linear_k.bias",
                                              A + "linear_v.bias", shape=(3 * d,))))
-        pp = empty(P2, d, dtype=cd, device=dev)
-        ops.linear(pos, b.w(A + "linear_pos.weight"), pp)
+        mode = L.self_attn.rel_mode
+        fused = fused_attn_ok(cd, dk, T, T)
+        if mode == REL_LEGACY and fused:
+            # the fused backward's d(q+v) GEMM runs over every physical column of the shifted band
+            # layout: `shift` zero rows in front of the table
+            shift = dbd_layout(T)[0]
+            pp_full = empty(shift + P2, d, dtype=cd, device=dev)
+            pp_full[:shift].zero_()
+            pp = pp_full[shift:]
+        else:
+            pp_full = None
+            pp = empty(P2, d, dtype=cd, device=dev)
+        if mode == REL_LEGACY:
+            # pos has T rows; the band is taken against Pext = [p; 0; p[:T-2]] (2T-1 rows)
+            assert pos.shape[0] == T
+            pT = empty(T, d, dtype=cd, device=dev)
+            ops.linear(pos, b.w(A + "linear_pos.weight"), pT)
+            lib.ea_legacy_pext(T, d, pT.data_ptr(), d, pp.data_ptr(), d, ops.dt(pp), ops.stream())
+        else:
+            ops.linear(pos, b.w(A + "linear_pos.weight"), pp)
         scale = 1.0 / math.sqrt(dk)
-        if fused_attn_ok(cd, dk, T, T):
+        if fused:
             # one kernel: (q+u)k^T + rel_shift((q+v)p^T), mask, softmax, dropout, @v
             O = empty(N, d, dtype=cd, device=dev)
             lse = empty(B * H * T, device=dev)
             dmask, ldm = attn_dmask(B * H * T, T, pa, dev)
-            lib.ea_attn_fused_fwd2(B, H, T, T, dk, qkv.data_ptr(), 3 * d, qkv[:, d:].data_ptr(), 3 * d,
-                                   qkv[:, 2 * d:].data_ptr(), 3 * d, b.f(A + "pos_bias_u").data_ptr(),
-                                   b.f(A + "pos_bias_v").data_ptr(), pp.data_ptr(), d, olens.data_ptr(), 0,
-                                   scale, float(pa), sd(3), O.data_ptr(), d, lse.data_ptr(), ops.ptr(dmask), ldm,
-                                   ops.stream())
+            lib.ea_attn_fused_fwd2_mode(B, H, T, T, dk, qkv.data_ptr(), 3 * d, qkv[:, d:].data_ptr(), 3 * d,
+                                        qkv[:, 2 * d:].data_ptr(), 3 * d, b.f(A + "pos_bias_u").data_ptr(),
+                                        b.f(A + "pos_bias_v").data_ptr(), pp.data_ptr(), d, olens.data_ptr(), 0,
+                                        scale, float(pa), sd(3), O.data_ptr(), d, lse.data_ptr(), ops.ptr(dmask), ldm,
+                                        mode, ops.stream())
             ldT = 0
-            s_core = ("fused", lse, dmask, ldm)
+            s_core = ("fused", lse, dmask, ldm, pp_full)
         else:
             qu = empty(N, d, dtype=cd, device=dev)
             qv = empty(N, d, dtype=cd, device=dev)
@@ -234,7 +255,7 @@ class ConformerBlockFn(torch.autograd.Function):
                      batch=B, nh=H, sA=(T * d, dk), sB=(0, dk), sC=(T * ldbd, B * T * ldbd), splitk=False)
             O, P, Pd, ldT = attn_fwd(qu, qkv[:, d:], qkv[:, 2 * d:], B=B, H=H, T1=T, T2=T, dk=dk,
                                      ldq=d, ldk=3 * d, ldv=3 * d, klen=olens, causal=False, scale=scale,
-                                     p=pa, seed=sd(3), cd=cd, bd=bd, ldbd=ldbd)
+                                     p=pa, seed=sd(3), cd=cd, bd=bd, ldbd=ldbd, rel_mode=mode)
             del bd
             s_core = ("unfused", qu, qv, P, Pd)
         x2 = empty(N, d, device=dev)
@@ -293,7 +314,7 @@ class ConformerBlockFn(torch.autograd.Function):
         x4, s_ff2 = _ffn_fwd(L, b, x3, "feed_forward", "norm_ff", p, sd(6), sd(7))
         out, mu5, rs5 = ln_fwd(x4, b, "norm_final", F32)
         ctx.L = L
-        ctx.meta = (B, T, d, H, dk, p, pa, seed, scale, ldT)
+        ctx.meta = (B, T, d, H, dk, p, pa, seed, scale, ldT, mode)
         ctx.save = (x0, x1, x2, x3, x4, s_ff1, (xn2, mu2, rs2, qkv, pp, O, s_core),
                     (xn3, mu3, rs3, g2, glu, y, z, bn_mean, bn_rstd), s_ff2, (mu5, rs5), pos, olens)
         return out.view(B, T, d)
@@ -303,7 +324,7 @@ class ConformerBlockFn(torch.autograd.Function):
         L = ctx.L
         b = L._b
         cd = b.cd
-        B, T, d, H, dk, p, pa, seed, scale, ldT = ctx.meta
+        B, T, d, H, dk, p, pa, seed, scale, ldT, mode = ctx.meta
         (x0, x1, x2, x3, x4, s_ff1, s_att, s_conv, s_ff2, (mu5, rs5), pos, olens) = ctx.save
         ctx.save = None
         li = L.layer_idx
@@ -369,10 +390,14 @@ class ConformerBlockFn(torch.autograd.Function):
         dqkv = empty(N, 3 * d, dtype=cd, device=dev)
         ldbd, shift = rup(P2, 8), 0
         if s_core[0] == "fused":
-            # dq includes the q+v path (dBD.p, in-kernel); dbd rows written in full, in the
-            # pipelined dQ pass's shifted layout (logical column r at r + shift); pos_bias_u /
-            # pos_bias_v gradients from per-block column sums of the two dq terms
-            _, lse, dmask, ldm = s_core
+            # dbd rows written in full, in the pipelined dQ pass's shifted layout (logical column r
+            # at r + shift); pos_bias_u / pos_bias_v gradients from per-block column sums of the dq
+            # terms.  Latest: dq includes the q+v path (dBD.p, in-kernel).  Legacy: the passes
+            # recompute the legacy scores and emit the band with the latest placement,
+            # ea_attn_legacy_band moves it onto the legacy rows, and d(q+v) is one batched GEMM
+            # over that band (the form of the unfused path below)
+            _, lse, dmask, ldm, pp_full = s_core
+            legacy = mode == REL_LEGACY
             shift, ldbd = dbd_layout(T)
             dbd = empty(H * B * T * ldbd, dtype=cd, device=dev)
             qv = empty(N, d, dtype=cd, device=dev)  # q + v, for the linear_pos weight gradient
@@ -383,16 +408,28 @@ class ConformerBlockFn(torch.autograd.Function):
                            klen=olens, causal=False, scale=scale, p=pa, seed=sd(3), O=O, ldo=d, lse=lse, dO=dO,
                            lddo=d, dq=dqkv, lddq=3 * d, dk=dqkv[:, d:], lddk=3 * d, dv=dqkv[:, 2 * d:],
                            lddv=3 * d, dbd=dbd, ldbd=ldbd, part=part, ldpart=d, qv_out=qv, ldqv=d, dmask=dmask,
-                           ldm=ldm, flags=1 | 2)
+                           ldm=ldm, flags=2 if legacy else 1 | 2, rel_mode=mode)
             ops.reduce_rows(part[:B * nqb * d], B * nqb, d, d, b.g(A + "pos_bias_u", shape=(d,)))
-            ops.reduce_rows(part[B * nqb * d:], B * nqb, d, d, b.g(A + "pos_bias_v", shape=(d,)))
+            if legacy:
+                raw = dbd
+                dbd = empty(H * B * T * ldbd, dtype=cd, device=dev)
+                lib.ea_attn_legacy_band(H * B, T, raw.data_ptr(), dbd.data_ptr(), ldbd, ops.stream())
+                del raw
+                dqv = empty(N, d, dtype=cd, device=dev)
+                ops.gemm(dbd, pp_full, dqv, M=T, N=dk, K=shift + P2, a_kmajor=1, b_kmajor=0, lda=ldbd, ldb=d, ldc=d,
+                         batch=B, nh=H, sA=(T * ldbd, B * T * ldbd), sB=(0, dk), sC=(T * d, dk), splitk=False)
+                ops.colsum(dqv, b.g(A + "pos_bias_v", shape=(d,)))
+                lib.ea_add_2d(N, d, dqv.data_ptr(), ops.dt(dqv), d, dqkv.data_ptr(), ops.dt(dqkv), 3 * d, 1.0,
+                              ops.stream())
+            else:
+                ops.reduce_rows(part[B * nqb * d:], B * nqb, d, d, b.g(A + "pos_bias_v", shape=(d,)))
         else:
             _, qu, qv, P, Pd = s_core
             dbd = empty(H * B * T * ldbd, dtype=cd, device=dev)
             attn_bwd(dO, qu, qkv[:, d:], qkv[:, 2 * d:], P, Pd, ldT, B=B, H=H, T1=T, T2=T, dk=dk,
                      ldq=d, ldk=3 * d, ldv=3 * d, scale=scale, p=pa, seed=sd(3), cd=cd,
                      dq=dqkv, lddq=3 * d, dk_=dqkv[:, d:], lddk=3 * d, dv=dqkv[:, 2 * d:], lddv=3 * d,
-                     dbd=dbd, ldbd=ldbd)
+                     dbd=dbd, ldbd=ldbd, rel_mode=mode)
             # q_u = q + u: du = sum dq_u ; q_v = q + v path: dq_v = dBD . p_h, dv_bias = sum dq_v
             dqv = empty(N, d, dtype=cd, device=dev)
             ops.gemm(dbd, pp, dqv, M=T, N=dk, K=P2, a_kmajor=1, b_kmajor=0, lda=ldbd, ldb=d, ldc=d,
@@ -413,7 +450,12 @@ class ConformerBlockFn(torch.autograd.Function):
                 dpp_full = empty(Mp, d, dtype=cd, device=dev)
                 ops.gemm(dbd, qv, dpp_full, M=Mp, N=dk, K=B * T, a_kmajor=0, b_kmajor=0, lda=ldbd, ldb=d, ldc=d,
                          batch=1, nh=H, sA=(0, B * T * ldbd), sB=(0, dk), sC=(0, dk))
-                ops.linear_dw(dpp_full[shift:], pos, b.g(A + "linear_pos.weight"), accumulate=True)
+                dpp = dpp_full[shift:]
+                if mode == REL_LEGACY:  # dp[k] = dPext[k] + dPext[T+1+k] over pos's T rows
+                    dpp = empty(T, d, dtype=cd, device=dev)
+                    lib.ea_legacy_pext_fold(T, d, dpp_full[shift:].data_ptr(), d, dpp.data_ptr(), d, ops.dt(dpp),
+                                            ops.stream())
+                ops.linear_dw(dpp, pos, b.g(A + "linear_pos.weight"), accumulate=True)
 
         fork = ops.fork_event()
         if fork is None:

@@ -95,6 +95,41 @@ class RelPositionalEncoding(nn.Module):
         return out
 
 
+def legacy_rel_pos_table(n, d):
+    """PositionalEncoding.extend_pe with reverse=True (embedding.py:58-79): row k holds the
+    sinusoid of position n-1-k."""
+    pos = torch.arange(n - 1, -1, -1.0, dtype=torch.float32).unsqueeze(1)
+    div = torch.exp(torch.arange(0, d, 2, dtype=torch.float32) * -(math.log(10000.0) / d))
+    pe = torch.zeros(n, d)
+    pe[:, 0::2] = torch.sin(pos * div)
+    pe[:, 1::2] = torch.cos(pos * div)
+    return pe
+
+
+class LegacyRelPositionalEncoding(RelPositionalEncoding):
+    """LegacyRelPositionalEncoding (embedding.py:220-257): pos_emb is the first T rows of the
+    reversed table.  The table has max_len rows until a forward sees a longer T; it is then
+    rebuilt with T rows and stays that size (extend_pe only ever grows it), so the rows a later,
+    shorter utterance gets depend on the longest one seen before: that state is kept here as
+    the reference keeps it in `pe`."""
+
+    def __init__(self, d_model, dropout_rate, max_len=5000):
+        super().__init__(d_model, dropout_rate, max_len)
+        self.n_rows = max_len  # rows of the reference's `pe` so far
+
+    def table(self, T, device):
+        self.n_rows = max(self.n_rows, T)
+        if self._pe is None or self._pe.shape[0] != self.n_rows or self._pe.device != device:
+            self._pe = legacy_rel_pos_table(self.n_rows, self.d_model).to(device)
+        return self._pe
+
+    def pos_emb(self, T, device, cd, training, seed):
+        src = self.table(T, device)[:T]
+        out = empty(T, self.d_model, dtype=cd, device=device)
+        ops.scale_dropout(src, out, 1.0, self.dropout_rate if training else 0.0, seed)
+        return out
+
+
 class Conv2dSubsampling(nn.Module):
     """Parameter holder with the reference's names: conv.0 / conv.2 / out.0 (+ pos_enc)."""
 

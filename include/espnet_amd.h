@@ -511,6 +511,30 @@ int ea_attn_softmax_bwd(int B, int H, int T1, int T2, float scale, const float* 
                         const float* P, long ldP, float p, unsigned long long seed, void* dS,
                         int ds_dtype, long ldS, void* dBD, long ldBD, void* stream);
 
+/* The rel-pos variant of the two softmax passes (rel_pos_type of the Conformer encoder):
+ * EA_REL_LATEST is the law above; EA_REL_LEGACY is LegacyRelPositionMultiHeadedAttention's
+ * rel_shift (attention.py:114-206), whose band BD_raw[r][k] = (q_r + v)·Pext[k] is taken
+ * against the extended table of ea_legacy_pext and read one query row lower in the strict
+ * upper triangle:
+ *   score[i,j] = S[i,j] + BD[i + (j > i)][T1-1-i+j]
+ *   dBD[r][k]  = dS[r, k-(T1-1-r)] for k in [T1-1-r, T1-1], dS[r-1, k-(T1-r)] for k in
+ *                [T1+1, 2*T1-1-r], 0 elsewhere (column T1 included); every row written in full.
+ * Legacy needs BD / dBD and no causal mask; any other rel_mode is EA_ERR_BAD_ARG. */
+enum { EA_REL_LATEST = 0, EA_REL_LEGACY = 1 };
+int ea_attn_softmax_fwd_mode(int B, int H, int T1, int T2, float scale, const float* S, long ldS,
+                             const float* BD, long ldBD, const long long* klen, int causal, float p,
+                             unsigned long long seed, float* P, long ldP, void* Pd, int pd_dtype,
+                             long ldPd, int rel_mode, void* stream);
+int ea_attn_softmax_bwd_mode(int B, int H, int T1, int T2, float scale, const float* dPd, long ldd,
+                             const float* P, long ldP, float p, unsigned long long seed, void* dS,
+                             int ds_dtype, long ldS, void* dBD, long ldBD, int rel_mode, void* stream);
+/* Pext (2T-1 rows x d, row stride ldx) from p = linear_pos(pos_emb) (T rows, row stride ldp):
+ * Pext[k] = p[k] for k < T, Pext[T] = 0, Pext[T+1+m] = p[m] for m <= T-3; both in `dtype`. */
+int ea_legacy_pext(int T, int d, const void* p, long ldp, void* pext, long ldx, int dtype, void* stream);
+/* Its adjoint: dp[k] = dPext[k] + dPext[T+1+k] (the second term for k <= T-3), summed in f32. */
+int ea_legacy_pext_fold(int T, int d, const void* dpext, long ldx, void* dp, long ldp, int dtype,
+                        void* stream);
+
 /* Fused attention core, head dim 64, bf16 q/k/v (relattn.hip): per (b, h)
  *   s[i,j] = ((q_i + bu)·k_j + (q_i + bv)·pp[T-1-i+j]) * scale   (pp != NULL: rel-pos,
  *            RelPositionMultiHeadedAttention with rel_shift, attention.py:262-305; T1 == T2)
@@ -532,6 +556,17 @@ int ea_attn_fused_fwd2(int B, int H, int T1, int T2, int dk, const void* q, long
                        const void* pp, long ldp, const long long* klen, int causal, float scale, float p,
                        unsigned long long seed, void* o, long ldo, float* lse, unsigned* dmask, int ldm,
                        void* stream);
+/* ea_attn_fused_fwd2 with the rel-pos variant: EA_REL_LATEST is the law above; EA_REL_LEGACY
+ * (pp = ea_legacy_pext's 2*T1-1 rows, no causal mask) is the legacy rel_shift,
+ *   s[i,j] = ((q_i + bu)·k_j + (q_{i + (j > i)} + bv)·pp[T-1-i+j]) * scale,
+ * rows >= T1 of q taken as zero.  The original forward kernel (EA_ATTN_FWD_V1=1, or operands
+ * past the 32-bit offset range) has no legacy form: EA_ERR_BAD_ARG there, as for any other
+ * rel_mode.  Backward: ea_attn_fused_bwd2_mode. */
+int ea_attn_fused_fwd2_mode(int B, int H, int T1, int T2, int dk, const void* q, long ldq, const void* k,
+                            long ldk, const void* v, long ldv, const float* bu, const float* bv,
+                            const void* pp, long ldp, const long long* klen, int causal, float scale,
+                            float p, unsigned long long seed, void* o, long ldo, float* lse,
+                            unsigned* dmask, int ldm, int rel_mode, void* stream);
 /* Backward of ea_attn_fused_fwd(2): dq = d(q + bu) (flags bit 0, pp only: + d(q + bv), the
  * rel-pos path dBD·pp computed in-kernel), dk, dv (bf16), and optionally:
  *   dbd (pp only, or NULL): the band dbd[h][b][i][T-1-i+j] = gradient of the raw rel-pos term
@@ -561,6 +596,24 @@ int ea_attn_fused_bwd2(int B, int H, int T1, int T2, int dk, const void* q, long
                        long lddo, void* dq, long lddq, void* dkout, long lddk, void* dvout, long lddv,
                        void* dbd, long lddbd, float* bias_part, long ldpart, void* qv_out, long ldqv,
                        const unsigned* dmask, int ldm, void* ws, long ws_bytes, int flags, void* stream);
+/* ea_attn_fused_bwd2 with the rel-pos variant.  EA_REL_LEGACY recomputes the scores with the
+ * legacy law (ea_attn_fused_fwd2_mode) in the pipelined passes only: flags must have bit 1 set
+ * and bit 0 clear (no in-kernel d(q + bv) term), no causal mask, and the original passes
+ * (EA_ATTN_BWDKV_V1=1, operands past the 32-bit offset range) are EA_ERR_BAD_ARG.  dbd is then
+ * still written with the latest placement, dS[i,j] at row i, column T-1-i+j (+ the layout's
+ * shift): ea_attn_legacy_band turns it into the legacy band, from which d(q + bv) = band·pp and
+ * d pp = band^T·(q + bv) follow as GEMMs. */
+int ea_attn_fused_bwd2_mode(int B, int H, int T1, int T2, int dk, const void* q, long ldq, const void* k,
+                       long ldk, const void* v, long ldv, const float* bu, const float* bv,
+                       const void* pp, long ldp, const long long* klen, int causal, float scale, float p,
+                       unsigned long long seed, const void* o, long ldo, const float* lse, const void* dO,
+                       long lddo, void* dq, long lddq, void* dkout, long lddk, void* dvout, long lddv,
+                       void* dbd, long lddbd, float* bias_part, long ldpart, void* qv_out, long ldqv,
+                       const unsigned* dmask, int ldm, void* ws, long ws_bytes, int flags, int rel_mode, void* stream);
+/* out[hb][r][k] = dbd[hb][r][k] for k <= T1-1, 0 for k == T1, dbd[hb][r-1][k] for k >= T1+1 (row
+ * 0: 0), k the logical column of ea_attn_dbd_layout's shifted rows (physical columns outside
+ * the band copied likewise: zeros); nhb = H*B blocks of T1 rows, bf16, out != dbd. */
+int ea_attn_legacy_band(long nhb, int T1, const void* dbd, void* out, long lddbd, void* stream);
 
 /* ---------------------------------------------------------------- losses */
 
