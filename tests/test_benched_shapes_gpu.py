@@ -24,14 +24,12 @@ XCD-contiguous (batch slice, K split, tile) mapping and the 7-way split-K weight
   max(2x the reference's own bf16 deviation at this architecture (tests/golden/c3_b2.npz
   ampdev), 2e-2).
 """
-import math
-
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
 from goldens import is_null_grad, regenerate_sized, section, sibling_weight
+from subsampling_ref import subsampling_f64 as _subsampling_f64
 from test_model_build import build
 
 pytestmark = pytest.mark.gpu
@@ -46,42 +44,6 @@ def _rel(a, b):
 
 
 # ---------------------------------------------------------------------------- subsampling
-def _bf(x):
-    return x.to(torch.bfloat16).to(torch.float64)
-
-
-def _subsampling_f64(P, feats, gy, emulate_bf16):
-    """Conv2dSubsampling fwd + bwd in float64 (dropout 0).  emulate_bf16: round where the
-    implicit-GEMM path stores bf16.  Returns (y, {param: grad})."""
-    r = _bf if emulate_bf16 else (lambda t: t)
-    W1, b1 = P["conv.0.weight"], P["conv.0.bias"]
-    W2, b2 = P["conv.2.weight"], P["conv.2.bias"]
-    Wl, bl = P["out.0.weight"], P["out.0.bias"]
-    C = W1.shape[0]
-    xs = math.sqrt(C)
-    x = feats.unsqueeze(1)
-    x1 = r(torch.relu(F.conv2d(x, W1, b1, stride=2)))              # (B, C, T1, F1)
-    W2r = r(W2)
-    x2 = r(torch.relu(F.conv2d(x1, W2r, b2, stride=2)))            # (B, C, T2, F2)
-    B, _, T2, F2 = x2.shape
-    xr = x2.transpose(1, 2).reshape(B, T2, C * F2)                   # subsampling.py:66-69
-    Wlr = r(Wl)
-    y = (xr @ Wlr.t() + bl) * xs
-    g = {}
-    gs = gy * xs
-    dv = r(gs)
-    g["out.0.bias"] = dv.reshape(-1, C).sum(0)  # the column sums of the (bf16) dv
-    g["out.0.weight"] = dv.reshape(-1, C).t() @ xr.reshape(-1, C * F2)
-    dxr = (dv @ Wlr).reshape(B, T2, C, F2).transpose(1, 2)           # (B, C, T2, F2)
-    dh2 = r(dxr * (x2 > 0))
-    g["conv.2.bias"] = dh2.sum((0, 2, 3))
-    g["conv.2.weight"] = torch.nn.grad.conv2d_weight(x1, W2.shape, dh2, stride=2)
-    dx1 = r(torch.nn.grad.conv2d_input(x1.shape, W2r, dh2, stride=2) * (x1 > 0))
-    g["conv.0.bias"] = dx1.sum((0, 2, 3))
-    g["conv.0.weight"] = torch.nn.grad.conv2d_weight(x, W1.shape, dx1, stride=2)
-    return y, g
-
-
 @pytest.mark.parametrize("B,T", [(32, 1000), (17, 2000)], ids=["c3_b32", "c5_b17_t2000"])
 def test_subsampling_bench_shapes_bf16_vs_float64(B, T):
     from espnet_amd.arena import ParamArena
