@@ -836,6 +836,38 @@ int ea_merge_conv_bwd(int B, int T, int C, int K, const void* xc, const void* dm
                       float p, unsigned long long seed_a, unsigned long long seed_b, void* dxc, float* dw,
                       float* dbias, int accumulate_params, float* workspace, long ws_elems, void* stream);
 
+
+/* ---------------------------------------------------------------- SequentialRNNLM (decoding) */
+
+/* K granule of the packed LSTM weights: the W_ih and the W_hh part of a row are each zero
+ * padded to a multiple of it. */
+enum { EA_LSTM_KG = 32 };
+
+/* One LSTM layer over one token of n hypotheses, in one launch (torch.nn.LSTM inside
+ * espnet2/lm/seq_rnn_lm.py:92-104, one time step):
+ *   gates = x . W_ih^T + h_prev[src] . W_hh^T + bias     (n, 4H), gate order i, f, g, o
+ *   c' = sigmoid(f) * c_prev[src] + sigmoid(i) * tanh(g);   h' = sigmoid(o) * tanh(c')
+ * Accumulation, activations and the state are f32.  I and H are any positive integers.
+ *  wpack (wdtype EA_F32 / EA_BF16, 16-B aligned): the packed weights.  Ip / Hp = I / H rounded
+ *    up to EA_LSTM_KG, K = Ip + Hp, row k-range [0, I) = W_ih, [Ip, Ip + H) = W_hh, the rest 0;
+ *    tile t holds hidden units 4t .. 4t+3 (units >= H: zero rows), its row 4*u + gate is row
+ *    gate*H + 4t + u of the torch weights; with SL = 16 (f32) / 32 (bf16) and nks = K / SL,
+ *    element (tile t, slice s, row r, j) is at ((t * nks + s) * 16 + r) * SL + j.
+ *    EA_BF16: x and h_prev are rounded to bf16 for the product (f32 accumulation).
+ *  bias (f32, 4H, 16-B aligned): bias[4 * unit + gate] = b_ih + b_hh of that gate row.
+ *  x (n rows, ldx >= I); with tok != NULL x is the embedding table (V rows, ldx) and row r
+ *    reads x[tok[r * ldtok]] (ids outside [0, V) are clamped).
+ *  h_prev, c_prev (n_prev rows, ldp >= H): read only.  src (n ints, or NULL = identity, then
+ *    n_prev >= n): the parent row of each hypothesis, any order, repeats allowed (indices outside
+ *    [0, n_prev) are clamped).
+ *  h_out, c_out (n rows, ldo >= H, distinct from h_prev / c_prev): columns [H, ldo) of rows
+ *    < n are written as zeros; rows >= n are not touched.  hb_out (bf16, same ldo, or NULL): a
+ *    bf16 copy of h_out for the bf16 output Linear. */
+int ea_lstm_step(int wdtype, int n, int I, int H, const void* wpack, const float* bias, const float* x,
+                 long ldx, const long long* tok, long ldtok, int V, const float* h_prev, const float* c_prev,
+                 long ldp, int n_prev, const int* src, float* h_out, float* c_out, long ldo,
+                 void* hb_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
