@@ -69,6 +69,9 @@ class ParamArena:
         self._params = named
         from . import hip_ops  # transposed bf16 copies for the Linear input-gradient GEMMs
         self.tshadow = hip_ops.attach_transposed_shadow(self.shadow)
+        # callables run after the weights changed (an optimizer step, refresh_shadow): packed
+        # copies a model keeps beside the arena are rebuilt there, on the stream
+        self.update_hooks = []
         self._flatten_buffers(model)
         with torch.no_grad():
             for n in layout:
@@ -134,6 +137,8 @@ class ParamArena:
                                  hip_ops.stream())
             if self.tshadow is not None:
                 self.tshadow.refresh()
+        for hook in self.update_hooks:
+            hook()
 
     def rebind(self):
         """Re-point Parameters at the arena (after an external .data / .grad reassignment)."""

@@ -8,9 +8,11 @@ and precomputed-feature corpora:
   allow_pickle=False.
 * ``text_int`` / ``text_float`` / ``csv_int`` / ``csv_float`` — load_num_sequence_text
   (espnet2/fileio/read_text.py:39-82).
+* ``text`` — read_2column_text (read_text.py:11-36): "uttA token token ..." -> the string after
+  the id; the task's preprocessor turns it into token ids.
 
-Types that need third-party decoders or a tokenizer (sound, kaldi_ark, text with a
-preprocessor, hdf5, ...) raise NotImplementedError naming the type.
+Types that need third-party decoders (sound, kaldi_ark, hdf5, ...) raise NotImplementedError
+naming the type.
 """
 from __future__ import annotations
 
@@ -82,6 +84,20 @@ class _NumSequence(collections.abc.Mapping):
         return len(self.data)
 
 
+class _Text(collections.abc.Mapping):
+    def __init__(self, path):
+        self.data = read_2column_text(path)
+
+    def __getitem__(self, key) -> str:
+        return self.data[key]
+
+    def __iter__(self):
+        return iter(self.data)
+
+    def __len__(self):
+        return len(self.data)
+
+
 def build_loader(path: str, loader_type: str):
     """dataset.py:_build_loader (:421-455) for the supported types."""
     if loader_type == "rand_float":
@@ -93,9 +109,11 @@ def build_loader(path: str, loader_type: str):
         return NpyScpReader(path)
     if loader_type in ("text_int", "text_float", "csv_int", "csv_float"):
         return _NumSequence(path, loader_type)
+    if loader_type == "text":
+        return _Text(path)
     raise NotImplementedError(f"loader_type={loader_type} is outside the build's data path "
                               "(supported: rand_float, rand_int_<low>_<high>, npy, text_int, text_float, "
-                              "csv_int, csv_float)")
+                              "csv_int, csv_float, text)")
 
 
 class ESPnetDataset:
@@ -139,7 +157,9 @@ class ESPnetDataset:
         data = {}
         for name, loader in self.loader_dict.items():
             v = loader[uid]
-            if isinstance(v, list):
+            if isinstance(v, str):
+                pass  # text: the preprocessor tokenises it (a string left over raises below)
+            elif isinstance(v, list):
                 v = np.array(v)
             elif isinstance(v, (int, float)):
                 v = np.array([v])

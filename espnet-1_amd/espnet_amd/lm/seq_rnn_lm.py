@@ -15,8 +15,15 @@ with their rows zero padded to a multiple of EA_LSTM_KG.  A step's states live i
 (2, nlayers, n, Hp) buffer; batch_score returns views of it and recognises them when they come
 back, so the beam's reordering costs an index vector and no copy.
 
-Inference only (eval forward without autograd): LM training, rnn_type other than lstm and
-tie_weights raise.
+prepare(train=True) adds the training path (rnn_train.py): in training mode with autograd,
+forward runs the embedding, the dropouts, one autograd node per LSTM layer (one GEMM for the
+input projection of all time steps, then ea_lstm_cell_fwd / ea_lstm_cell_bwd once per step) and
+the output Linear over the whole padded batch.  The recurrent kernels' packs of weight_hh are
+rebuilt on the device after every optimizer step (ParamArena.update_hooks) and the scorer's
+packs lazily at the next eval call, so one object trains, validates and scores.  Under
+torch.no_grad() a model in training mode takes the scorer's path (no dropout, nothing saved).  Without
+train=True the model is a decoding scorer: a training-mode forward with autograd raises.
+rnn_type other than lstm and tie_weights raise.
 """
 from __future__ import annotations
 
@@ -28,6 +35,8 @@ from torch import nn
 from .. import hip_ops as ops
 from .._lib import BF16, F32, LSTM_KG, lib
 from ..arena import ParamArena
+from ..layers.common import site_seed
+from .rnn_train import DropFn, EmbedFn, HHPacks, LSTMLayerFn, OutLinearFn, pack_lstm_hh, pack_lstm_hh_t  # noqa: F401
 
 KG = LSTM_KG  # K granule of the packed operands
 TILE_UNITS = 4  # hidden units per weight tile (x 4 gates = 16 rows, one MFMA column tile)
@@ -104,14 +113,25 @@ class SequentialRNNLM(nn.Module):
         return h, c
 
     # ------------------------------------------------------------------ device copies
-    def prepare(self, device="cuda", amp: bool = False):
+    def prepare(self, device="cuda", amp: bool = False, train: bool = False, seed: int = 0, *, owner=None):
         """Move the parameters into a flat arena on the GPU and build the packed operands
-        (amp: bf16 LSTM and output-Linear weights, half the bytes streamed per step)."""
+        (amp: bf16 LSTM and output-Linear weights, half the bytes streamed per step).
+        train: also build the training path (bf16 weight shadow under amp, the recurrent
+        kernels' packs, dropout streams drawn from `seed` and the step counter).
+        owner: the module that holds this one as its attribute `lm` (ESPnetLanguageModel); the
+        arena is then laid out over the owner's parameter names, which the optimizer uses."""
         device = torch.device(device)
         if device.type != "cuda":
             raise RuntimeError("espnet_amd runs on the GPU only (no CPU fallback)")
         self._cd, self._device = (torch.bfloat16 if amp else torch.float32), device
-        self.arena = ParamArena(self, device)
+        self._train, self._seed, self._nstep, self._stale = bool(train), int(seed), 0, False
+        self._prefix = "" if owner is None else "lm."
+        self.arena = ParamArena(self if owner is None else owner, device, shadow_dtype=self._cd if train else None)
+        if train:
+            self._anchor = torch.zeros(1, device=device, requires_grad=True)
+            self._pe0 = torch.zeros(1, self.ninp, device=device)  # ea_embed_fwd adds a position row
+            self._hh = [HHPacks(getattr(self.rnn, f"weight_hh_l{k}"), self._cd) for k in range(self.nlayers)]
+            self.arena.update_hooks.append(self._weights_changed)
         self._recent = {}  # storage pointer -> (state buffer, states handed out) of the last two steps
         self._handed = {}  # id(state tuple) -> (the tuple, its buffer, its row)
         self.repack()
@@ -120,9 +140,24 @@ class SequentialRNNLM(nn.Module):
             self.__dict__["_hooked"] = True
         return self
 
+    def _weights_changed(self):
+        """After an optimizer step (or a shadow refresh): the recurrent packs now, on the
+        stream, the scorer's packs at the next eval call."""
+        for k, hh in enumerate(self._hh):
+            hh.refresh(getattr(self.rnn, f"weight_hh_l{k}"))
+        self._stale = True
+
+    def _w(self, name: str) -> torch.Tensor:
+        """A weight in the compute dtype: the arena's bf16 shadow under amp, else the master."""
+        return self.arena.view(self._prefix + name, which="shadow" if self._cd == torch.bfloat16 else "data")
+
     @torch.no_grad()
     def repack(self):
         cd = self._cd
+        self._stale = False
+        if self._train:
+            self.arena.refresh_shadow()  # (runs the update hooks: the recurrent packs)
+            self._stale = False
         self._emb = _pad_cols(self.encoder.weight, torch.float32)
         self._wpack, self._bias = [], []
         for k in range(self.nlayers):
@@ -174,7 +209,10 @@ class SequentialRNNLM(nn.Module):
         if self.arena is None:
             raise RuntimeError("SequentialRNNLM.prepare(device) first")
         if torch.is_grad_enabled() and self.training:
-            raise NotImplementedError("espnet_amd SequentialRNNLM is a decoding scorer (no training)")
+            raise NotImplementedError("espnet_amd SequentialRNNLM is a decoding scorer (no training): "
+                                      "prepare(device, train=True) builds the training path")
+        if self._stale:
+            self.repack()
 
     def _remember(self, buf: torch.Tensor, states: List[Any]):
         """Keep the last two steps' buffers and the state tuples handed out for them alive: a
@@ -290,9 +328,52 @@ class SequentialRNNLM(nn.Module):
         """(B, T) ids, hidden None or (h, c) of (L, B, H) -> ((B, T, vocab) logits, (h, c)).
         Loops over T with the step kernel (T x nlayers launches and one output Linear): this is
         the scoring interface for whole sentences, not the decoding path, which is batch_score."""
+        if self.arena is not None and self._train and self.training and torch.is_grad_enabled():
+            return self._forward_train(input, hidden)
         self._check()
         with torch.no_grad():
             return self._forward(input, hidden)
+
+    def dropout_seeds(self, nstep: int) -> dict:
+        """The ea_scale_dropout streams of training forward number `nstep` (0 = the first after
+        prepare): "embed" (self.drop on the embedding, (T*B, ninp) time-major), "rnn{k}"
+        (nn.LSTM's dropout on layer k's output, k < nlayers - 1, (T*B, nhid)) and "out"
+        (self.drop on the last layer's output)."""
+        base = site_seed(self._seed, 0, nstep)
+        seeds = {"embed": site_seed(base, 1, 0), "out": site_seed(base, 1, 1)}
+        seeds.update({f"rnn{k}": site_seed(base, 2, k) for k in range(self.nlayers - 1)})
+        return seeds
+
+    def _forward_train(self, input, hidden):
+        """The training forward over the whole padded batch (nn.LSTM without packing, as the
+        reference runs it): time-major rows inside, (B, T, vocab) logits out.  hidden: constants."""
+        V, L, H = self.vocab_size, self.nlayers, self.nhid
+        ids = input.to(self._device, torch.int64)
+        B, T = ids.shape
+        if B == 0 or T == 0:
+            raise ValueError(f"empty batch: {tuple(ids.shape)}")
+        tok = ids.t().clamp(0, V - 1).contiguous().view(-1)  # row t * B + b
+        seeds = self.dropout_seeds(self._nstep)
+        self._nstep += 1
+        p, p_rnn = float(self.drop.p), float(self.rnn.dropout)
+        x = EmbedFn.apply(self._anchor, tok, self)
+        if p > 0.0:
+            x = DropFn.apply(x, p, seeds["embed"])
+        hn, cn = [], []
+        for k in range(L):
+            h0 = c0 = None
+            if hidden is not None:
+                h0 = hidden[0][k].detach().to(self._device, torch.float32)
+                c0 = hidden[1][k].detach().to(self._device, torch.float32)
+            x, h, c = LSTMLayerFn.apply(x, self, k, T, B, h0, c0)
+            hn.append(h)
+            cn.append(c)
+            if k < L - 1 and p_rnn > 0.0:
+                x = DropFn.apply(x, p_rnn, seeds[f"rnn{k}"])
+        if p > 0.0:
+            x = DropFn.apply(x, p, seeds["out"])
+        y = OutLinearFn.apply(x, self)
+        return y.view(T, B, V).transpose(0, 1), (torch.stack(hn), torch.stack(cn))
 
     def _forward(self, input, hidden):
         ids = input.to(self._device, torch.int64).contiguous()

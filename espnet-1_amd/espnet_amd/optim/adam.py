@@ -79,6 +79,8 @@ class ArenaAdam(torch.optim.Optimizer):
                              ops.ptr(grad_norm), float(max_norm), ops.stream())
         if getattr(a, "tshadow", None) is not None:  # W^T copies follow the new bf16 shadow
             a.tshadow.refresh()
+        for hook in getattr(a, "update_hooks", ()):  # packed copies kept beside the arena
+            hook()
 
     def zero_grad(self, set_to_none: bool = False):
         self.arena.grad.zero_()

@@ -104,6 +104,10 @@ def _stamp(phase):
 
 
 class Trainer:
+    # run() replays captured steps (train/graph.py, shaped after the ASR model's batch); a
+    # subclass with False launches every step eagerly
+    capture_steps = True
+
     def __init__(self):
         raise RuntimeError("This class can't be instantiated.")
 
@@ -349,9 +353,11 @@ class Trainer:
         dp = ArenaDataParallel(model) if distributed else None
         # steps whose shapes repeat are captured and replayed; with accum_grad > 1 the micro-step
         # and the updating micro-step are two graphs per shape
-        runner = CapturedTrainStep(model, optimizers[0], schedulers[0] if schedulers else None,
-                                   grad_clip=opts.grad_clip, dp=dp, warmup=2, accum_grad=opts.accum_grad,
-                                   control_group=getattr(distributed_option, "control_group", None))
+        runner = None
+        if cls.capture_steps:
+            runner = CapturedTrainStep(model, optimizers[0], schedulers[0] if schedulers else None,
+                                       grad_clip=opts.grad_clip, dp=dp, warmup=2, accum_grad=opts.accum_grad,
+                                       control_group=getattr(distributed_option, "control_group", None))
         all_invalid = False
         for iepoch in range(start_epoch, opts.max_epoch + 1):
             logging.info(f"{iepoch}/{opts.max_epoch}epoch started")

@@ -868,6 +868,55 @@ int ea_lstm_step(int wdtype, int n, int I, int H, const void* wpack, const float
                  long ldp, int n_prev, const int* src, float* h_out, float* c_out, long ldo,
                  void* hb_out, void* stream);
 
+/* ---------------------------------------------------------------- SequentialRNNLM (training) */
+
+/* The recurrent half of one LSTM layer's training step, one launch per time step; the time loop
+ * is the caller's.  The input projection xproj = X . W_ih^T + (b_ih + b_hh) of all time steps
+ * and the non-recurrent backward products (dW_hh = dgates^T . H_prev, dW_ih = dgates^T . X,
+ * dX = dgates . W_ih, db = colsum(dgates)) are ea_gemm / ea_colsum calls over all T * B rows.
+ * Accumulation, activations, states and gradients are f32; wdtype EA_BF16 multiplies bf16
+ * operands (the pack and a bf16 h / dgates).  H is any positive integer, n >= 0 (0: no launch).
+ *
+ * Packs (16-B aligned, SL = 16 (f32) / 32 (bf16) elements per slice, zero filled):
+ *  pack_lstm_hh   (forward): the W_hh part of ea_lstm_step's pack on its own.  K = Hp = H rounded
+ *    up to EA_LSTM_KG, nks = Hp / SL; tile t holds hidden units 4t .. 4t+3, its row 4*u + gate is
+ *    row gate*H + 4t + u of weight_hh; element (t, s, r, j) at ((t * nks + s) * 16 + r) * SL + j
+ *    = weight_hh[gate*H + 4t + u, s * SL + j].  ceil(H / 4) tiles.
+ *  pack_lstm_hh_t (backward): the transpose.  K = Gp = 4H rounded up to EA_LSTM_KG, nks = Gp / SL;
+ *    tile t holds hidden units 16t .. 16t+15 as its rows; element (t, s, r, j) at the same address
+ *    formula = weight_hh[s * SL + j, 16t + r].  ceil(H / 16) tiles.
+ *
+ * ea_lstm_cell_fwd:  gates = xproj + h_prev . W_hh^T (gate order i, f, g, o);
+ *   c = sigmoid(f) c_prev + sigmoid(i) tanh(g);  h = sigmoid(o) tanh(c)
+ *  xproj (n rows, ldx >= 4H): column gate*H + unit, bias included.
+ *  h_prev (f32; bf16 with EA_BF16), c_prev (f32): n rows, ldp >= H elements, read only.
+ *  h_out, c_out (f32, n rows, ldo >= H), hb_out (bf16 copy of h_out, same ldo; required with
+ *    EA_BF16, else optional): columns [H, ldo) of rows < n are written as zeros.  None may alias
+ *    h_prev / c_prev.
+ *  gates (f32, n rows, ldg >= 4H, ldg % 4 == 0, 16-B aligned): the ACTIVATED gates,
+ *    gates[row*ldg + 4*unit + (0..3)] = sigmoid(i), sigmoid(f), tanh(g), sigmoid(o).
+ *
+ * ea_lstm_cell_bwd (called for t = T-1 .. 0):
+ *   dh = dh_out + dgates_next . W_hh          (dgates_next NULL, the first call: dh = dh_out)
+ *   do = dh tanh(c) o (1 - o);  dc = dc_in + dh o (1 - tanh(c)^2)
+ *   di = dc g i (1 - i);  df = dc c_prev f (1 - f);  dg = dc i (1 - g^2);  dc_out = dc f
+ *  dgates_next (n rows, lddn >= 4H; f32, or with EA_BF16 the bf16 dgates_b of the call before).
+ *  dh_out (f32, n rows, lddh >= H, or NULL = 0): the gradient arriving at this step's h.
+ *  gates: ea_lstm_cell_fwd's of this step; c, c_prev (f32, ldc >= H): c_t and c_{t-1}.
+ *  dc_in (NULL = 0) / dc_out (f32, lddc >= H, distinct): the cell-state gradient carried to t-1;
+ *    columns [H, lddc) of dc_out are written as zeros.
+ *  dgates (f32) and dgates_b (bf16 copy; required with EA_BF16): n rows, ldd >= 4H, column
+ *    gate*H + unit (torch's order: the GEMMs above take them as they are), [4H, ldd) zeros.
+ *    Neither may alias dgates_next.
+ *  dh_tot (f32, ldt >= H, or NULL): receives dh (dh_out plus the recurrent part). */
+int ea_lstm_cell_fwd(int wdtype, int n, int H, const void* wpack, const float* xproj, long ldx,
+                     const void* h_prev, const float* c_prev, long ldp, float* h_out, float* c_out,
+                     long ldo, void* hb_out, float* gates, long ldg, void* stream);
+int ea_lstm_cell_bwd(int wdtype, int n, int H, const void* wpack_t, const void* dgates_next, long lddn,
+                     const float* dh_out, long lddh, const float* gates, long ldg, const float* c,
+                     const float* c_prev, long ldc, const float* dc_in, float* dc_out, long lddc,
+                     float* dgates, void* dgates_b, long ldd, float* dh_tot, long ldt, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
