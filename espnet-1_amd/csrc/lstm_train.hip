@@ -13,127 +13,15 @@
 //             include/espnet_amd.h); the first launch (t = T - 1) has no dgates[t+1] and skips
 //             the product.
 //
-// Both are the weight-stream shape of rnn_lm.hip's lstm_step_kernel with B a training batch: a
-// block owns up to 64 rows (MT row tiles) x NJ column tiles and ALL of K; its 8 waves split K
-// slice-wise, each keeping U slices of loads in flight, operands go global -> registers in MFMA
-// fragment order (the weight is used once per block, nothing is shared between waves), the
-// waves' partial tiles are summed through LDS and the epilogue runs on the sums in f32.  Rows
-// beyond 64 go to further block rows (grid.y); those re-read the weights, from L2 / MALL for
-// every block row but the first.  The forward's column tile is 4 hidden units x 4 gates (so the
-// cell update is local to the tile), the backward's is 16 hidden units.  No block waits for
-// another: the time loop is the host's.
-//
-// Packs (espnet_amd/lm/seq_rnn_lm.py pack_lstm_hh / pack_lstm_hh_t, layout in the header).
-#include "common.h"
+// Both run on lstm_core.h's block product with B a training batch.  The forward's column tile
+// is 4 hidden units x 4 gates (so the cell update is local to the tile and is the decoding
+// step's), the backward's is 16 hidden units with a cell-gradient epilogue of its own.  The
+// time loop is the host's.
+#include "lstm_core.h"
 
 namespace {
 
-constexpr int LT_W = 8;  // waves per block (K split)
-
-template <bool BF> struct Frag;
-template <> struct Frag<false> { typedef f32x4 T; typedef float W; };
-template <> struct Frag<true> { typedef bf16x8 T; typedef bf16 W; };
-
-// the lane's AN operand elements k .. k + AN - 1 of a row; elements >= lim are 0.
-// `fast` (wave-uniform): the whole slice lies below lim and the row is 16-B aligned.
-template <bool BF>
-EA_DEV typename Frag<BF>::T load_a(const typename Frag<BF>::W* __restrict__ row, int k, int lim, bool fast) {
-  constexpr int AN = BF ? 8 : 4;
-  typedef typename Frag<BF>::T frag;
-  if (fast) return *(const frag*)(row + k);
-  frag out;
-#pragma unroll
-  for (int e = 0; e < AN; ++e) {
-    if (k + e < lim)
-      out[e] = row[k + e];
-    else
-      out[e] = (typename Frag<BF>::W)0.f;
-  }
-  return out;
-}
-
-EA_DEV float sigmoid_exact(float x) { return 1.f / (1.f + expf(-x)); }
-
-// acc = A(rows of the block, K) . pack(column tiles t0 .. t0 + NJ - 1)^T summed over the block's
-// waves: on return red[q][row][col], q < LT_W / 2, hold four partial sums of every element
-// (the epilogue adds them).  ar[i]: the lane's operand row of row tile i.
-template <bool BF, int MT, int NJ, int U>
-EA_DEV void block_product(const typename Frag<BF>::W* const (&ar)[MT], int lim, bool avec, const void* wpack, int nks,
-                          int t0, int ntiles, float (*red)[16 * MT][16 * NJ + 4]) {
-  typedef typename Frag<BF>::W WT;
-  typedef typename Frag<BF>::T frag;
-  constexpr int SL = BF ? 32 : 16;  // K depth of one slice (one 16-B load per lane)
-  constexpr int AN = BF ? 8 : 4;    // operand elements per lane per slice
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int lr = lane & 15, g = lane >> 4;
-  const WT* bp[NJ];
-  bool bok[NJ];
-#pragma unroll
-  for (int j = 0; j < NJ; ++j) {
-    bok[j] = t0 + j < ntiles;
-    bp[j] = (const WT*)wpack + ((long)(bok[j] ? t0 + j : 0) * nks * 16 + lr) * SL + g * AN;
-  }
-  f32x4 acc[MT][NJ];
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const frag zero = {};
-
-  for (int s0 = w; s0 < nks; s0 += LT_W * U) {
-    frag a[U][MT], b[U][NJ];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int s = s0 + u * LT_W;
-      const bool in = s < nks;
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) b[u][j] = in && bok[j] ? *(const frag*)(bp[j] + (long)s * 16 * SL) : zero;
-      const bool fast = avec && (s + 1) * SL <= lim;
-#pragma unroll
-      for (int i = 0; i < MT; ++i) a[u][i] = in ? load_a<BF>(ar[i], s * SL + g * AN, lim, fast) : zero;
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-#pragma unroll
-      for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-          if constexpr (BF) {
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[u][i], b[u][j], acc[i][j], 0, 0, 0);
-          } else {
-            // four 4-deep steps: step e takes element e of every lane's 16-B chunk (the same
-            // k permutation on both operands)
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-              acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u][i][e], b[u][j][e], acc[i][j], 0, 0, 0);
-          }
-        }
-  }
-
-  // waves 4-7 through LDS into waves 0-3 (D layout: the lane holds rows 4 * (lane >> 4) + r of
-  // column lane & 15)
-  if (w >= LT_W / 2) {
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-      for (int j = 0; j < NJ; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) red[w - LT_W / 2][i * 16 + 4 * g + r][j * 16 + lr] = acc[i][j][r];
-  }
-  __syncthreads();
-  if (w < LT_W / 2) {
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-      for (int j = 0; j < NJ; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          float* q = &red[w][i * 16 + 4 * g + r][j * 16 + lr];
-          *q = acc[i][j][r] + *q;
-        }
-  }
-  __syncthreads();
-}
+using namespace lstm_core;
 
 // ------------------------------------------------------------------ forward
 struct CellFwdP {
@@ -154,77 +42,24 @@ struct CellFwdP {
 };
 
 template <bool BF, int MT, int NJ, int U>
-__global__ __launch_bounds__(64 * LT_W) void lstm_cell_fwd_kernel(CellFwdP p) {
+__global__ __launch_bounds__(64 * NW) void lstm_cell_fwd_kernel(CellFwdP p) {
   typedef typename Frag<BF>::W WT;
-  constexpr int SL = BF ? 32 : 16;
-  constexpr int BR = 16 * MT, LD = 16 * NJ + 4;
-  __shared__ __attribute__((aligned(16))) float red[LT_W / 2][BR][LD];
-  const int lr = threadIdx.x & 15;
-  const int r0 = blockIdx.y * BR, t0 = blockIdx.x * NJ;
-  const int ntiles = (p.H + 3) / 4;
+  __shared__ __attribute__((aligned(16))) float red[NW / 2][16 * MT][16 * NJ + 4];
+  const int r0 = blockIdx.y * 16 * MT, t0 = blockIdx.x * NJ;
 
-  const WT* hr[MT];
+  RowsA<BF, MT, WT> a;
+  a.lim = p.H; a.vec = p.hvec;
 #pragma unroll
-  for (int i = 0; i < MT; ++i) {
-    const int row = r0 + i * 16 + lr;
-    hr[i] = (const WT*)p.hp + (long)(row < p.n ? row : 0) * p.ldp;  // rows >= n are never stored
-  }
-  block_product<BF, MT, NJ, U>(hr, p.H, p.hvec, p.w, p.Hp / SL, t0, ntiles, red);
+  for (int i = 0; i < MT; ++i) a.row[i] = (const WT*)p.hp + (long)lane_row(r0, i, p.n) * p.ldp;
+  block_product<BF, MT, NJ, U>(a, p.w, p.Hp / (BF ? 32 : 16), t0, (p.H + 3) / 4, red);
 
-  constexpr int CELLS = BR * NJ * 4;  // (row, hidden unit) pairs of the block
-  for (int ci = threadIdx.x; ci < CELLS; ci += 64 * LT_W) {
-    const int lrow = ci / (NJ * 4), cu = ci % (NJ * 4);  // cu = 4 * (tile in block) + unit in tile
-    const int row = r0 + lrow, unit = t0 * 4 + cu;
-    if (row >= p.n || unit >= p.H) continue;
-    float4 s = *(const float4*)&red[0][lrow][cu * 4];
-#pragma unroll
-    for (int q = 1; q < LT_W / 2; ++q) {
-      const float4 t = *(const float4*)&red[q][lrow][cu * 4];
-      s.x += t.x; s.y += t.y; s.z += t.z; s.w += t.w;
-    }
-    const float* xp = p.xproj + (long)row * p.ldx + unit;  // torch gate order: column gate * H + unit
-    const float cprev = p.cp[(long)row * p.ldp + unit];
-    const float gi = sigmoid_exact(s.x + xp[0]), gf = sigmoid_exact(s.y + xp[p.H]);
-    const float gg = tanhf(s.z + xp[2 * (long)p.H]), go = sigmoid_exact(s.w + xp[3 * (long)p.H]);
-    const float c = gf * cprev + gi * gg;
-    const float h = go * tanhf(c);
-    p.co[(long)row * p.ldo + unit] = c;
-    p.ho[(long)row * p.ldo + unit] = h;
-    if (p.hb) p.hb[(long)row * p.ldo + unit] = (bf16)h;
-    *(float4*)(p.gates + (long)row * p.ldg + 4 * unit) = make_float4(gi, gf, gg, go);
-  }
-
-  // pad columns [H, ldo) of this row group: zeros (the next step, the next layer and the
-  // GEMMs over the sequence read them against zero weight columns)
-  if (blockIdx.x == gridDim.x - 1) {
-    const int padw = (int)(p.ldo - p.H);
-    const int rows = min(BR, p.n - r0);
-    for (int idx = threadIdx.x; idx < rows * padw; idx += 64 * LT_W) {
-      const long o = (long)(r0 + idx / padw) * p.ldo + p.H + idx % padw;
-      p.ho[o] = 0.f;
-      p.co[o] = 0.f;
-      if (p.hb) p.hb[o] = (bf16)0.f;
-    }
-  }
-}
-
-template <bool BF, int MT, int NJ>
-int launch_fwd(const CellFwdP& p, hipStream_t st) {
-  constexpr int U = MT == 4 ? 4 : 8;
-  dim3 grid(ea_cdiv((p.H + 3) / 4, NJ), ea_cdiv(p.n, 16 * MT), 1);
-  hipLaunchKernelGGL((lstm_cell_fwd_kernel<BF, MT, NJ, U>), grid, dim3(64 * LT_W), 0, st, p);
-  EA_LAUNCH_CHECK();
-  return 0;
-}
-
-template <bool BF>
-int launch_fwd_mt(const CellFwdP& p, hipStream_t st) {
-  // a training batch fills 64-row blocks; the narrow row tiles serve B < 64 (the last batch of
-  // an epoch, validation).  Two column tiles per block from H = 1024 up, as ea_lstm_step does.
-  const bool wide = (p.H + 3) / 4 >= 256;
-  if (p.n <= 16) return wide ? launch_fwd<BF, 1, 2>(p, st) : launch_fwd<BF, 1, 1>(p, st);
-  if (p.n <= 32) return wide ? launch_fwd<BF, 2, 2>(p, st) : launch_fwd<BF, 2, 1>(p, st);
-  return wide ? launch_fwd<BF, 4, 2>(p, st) : launch_fwd<BF, 4, 1>(p, st);
+  cell_fwd_epilogue<MT, NJ>(
+      red, r0, t0, p.n, p.H,
+      [&](int row, int unit) {
+        const float* xp = p.xproj + (long)row * p.ldx + unit;  // torch gate order: column gate * H + unit
+        return make_float4(xp[0], xp[p.H], xp[2 * (long)p.H], xp[3 * (long)p.H]);
+      },
+      [&](int row, int unit) { return p.cp[(long)row * p.ldp + unit]; }, p.ho, p.co, p.hb, p.ldo, p.gates, p.ldg);
 }
 
 // ------------------------------------------------------------------ backward
@@ -252,39 +87,28 @@ struct CellBwdP {
 };
 
 template <bool BF, int MT, int U>
-__global__ __launch_bounds__(64 * LT_W) void lstm_cell_bwd_kernel(CellBwdP p) {
+__global__ __launch_bounds__(64 * NW) void lstm_cell_bwd_kernel(CellBwdP p) {
   typedef typename Frag<BF>::W WT;
-  constexpr int SL = BF ? 32 : 16;
-  constexpr int BR = 16 * MT, LD = 16 + 4;
-  __shared__ __attribute__((aligned(16))) float red[LT_W / 2][BR][LD];
-  const int lr = threadIdx.x & 15;
-  const int r0 = blockIdx.y * BR, t0 = blockIdx.x;
-  const int ntiles = (p.H + 15) / 16;
+  __shared__ __attribute__((aligned(16))) float red[NW / 2][16 * MT][16 + 4];
+  const int r0 = blockIdx.y * 16 * MT, t0 = blockIdx.x;
   const bool rec = p.dgn != nullptr;  // uniform over the launch
 
   if (rec) {
-    const WT* ar[MT];
+    RowsA<BF, MT, WT> a;
+    a.lim = p.G; a.vec = p.avec;
 #pragma unroll
-    for (int i = 0; i < MT; ++i) {
-      const int row = r0 + i * 16 + lr;
-      ar[i] = (const WT*)p.dgn + (long)(row < p.n ? row : 0) * p.lddn;
-    }
+    for (int i = 0; i < MT; ++i) a.row[i] = (const WT*)p.dgn + (long)lane_row(r0, i, p.n) * p.lddn;
     const int Gp = (p.G + EA_LSTM_KG - 1) / EA_LSTM_KG * EA_LSTM_KG;
-    block_product<BF, MT, 1, U>(ar, p.G, p.avec, p.wt, Gp / SL, t0, ntiles, red);
+    block_product<BF, MT, 1, U>(a, p.wt, Gp / (BF ? 32 : 16), t0, (p.H + 15) / 16, red);
   }
 
-  constexpr int CELLS = BR * 16;
-  for (int ci = threadIdx.x; ci < CELLS; ci += 64 * LT_W) {
+  constexpr int CELLS = 16 * MT * 16;
+  for (int ci = threadIdx.x; ci < CELLS; ci += 64 * NW) {
     const int lrow = ci / 16, cu = ci % 16;
     const int row = r0 + lrow, unit = t0 * 16 + cu;
     if (row >= p.n || unit >= p.H) continue;
     float dh = p.dho ? p.dho[(long)row * p.lddh + unit] : 0.f;
-    if (rec) {
-      float s = red[0][lrow][cu];
-#pragma unroll
-      for (int q = 1; q < LT_W / 2; ++q) s += red[q][lrow][cu];
-      dh += s;
-    }
+    if (rec) dh += sum_partials<float>(red, lrow, cu);
     const float4 a = *(const float4*)(p.gates + (long)row * p.ldg + 4 * unit);  // i, f, g, o
     const float tc = tanhf(p.c[(long)row * p.ldc + unit]);
     const float cp = p.cprev[(long)row * p.ldc + unit];
@@ -304,37 +128,10 @@ __global__ __launch_bounds__(64 * LT_W) void lstm_cell_bwd_kernel(CellBwdP p) {
     if (p.dht) p.dht[(long)row * p.ldt + unit] = dh;
   }
 
-  // pad columns [4H, ldd) of dgates and [H, lddc) of the carry: zeros
-  if (blockIdx.x == gridDim.x - 1) {
-    const int rows = min(BR, p.n - r0);
-    const int padg = (int)(p.ldd - p.G), padc = (int)(p.lddc - p.H);
-    for (int idx = threadIdx.x; idx < rows * padg; idx += 64 * LT_W) {
-      const long o = (long)(r0 + idx / padg) * p.ldd + p.G + idx % padg;
-      p.dg[o] = 0.f;
-      if (p.dgb) p.dgb[o] = (bf16)0.f;
-    }
-    for (int idx = threadIdx.x; idx < rows * padc; idx += 64 * LT_W)
-      p.dco[(long)(r0 + idx / padc) * p.lddc + p.H + idx % padc] = 0.f;
-  }
+  // pad columns [4H, ldd) of dgates and [H, lddc) of the carry
+  zero_pad<16 * MT>(r0, p.n, p.G, p.ldd, p.dg, nullptr, p.dgb);
+  zero_pad<16 * MT>(r0, p.n, p.H, p.lddc, p.dco, nullptr, nullptr);
 }
-
-template <bool BF, int MT>
-int launch_bwd(const CellBwdP& p, hipStream_t st) {
-  constexpr int U = MT == 4 ? 4 : 8;
-  dim3 grid(ea_cdiv(p.H, 16), ea_cdiv(p.n, 16 * MT), 1);
-  hipLaunchKernelGGL((lstm_cell_bwd_kernel<BF, MT, U>), grid, dim3(64 * LT_W), 0, st, p);
-  EA_LAUNCH_CHECK();
-  return 0;
-}
-
-template <bool BF>
-int launch_bwd_mt(const CellBwdP& p, hipStream_t st) {
-  if (p.n <= 16) return launch_bwd<BF, 1>(p, st);
-  if (p.n <= 32) return launch_bwd<BF, 2>(p, st);
-  return launch_bwd<BF, 4>(p, st);
-}
-
-bool aligned16(const void* q) { return ((uintptr_t)q & 15) == 0; }
 
 }  // namespace
 
@@ -355,7 +152,13 @@ extern "C" int ea_lstm_cell_fwd(int wdtype, int n, int H, const void* wpack, con
   p.w = wpack; p.xproj = xproj; p.ldx = ldx; p.hp = h_prev; p.cp = c_prev; p.ldp = ldp;
   p.ho = h_out; p.co = c_out; p.ldo = ldo; p.hb = (bf16*)hb_out; p.gates = gates; p.ldg = ldg;
   p.hvec = aligned16(h_prev) && ldp % (wdtype == EA_BF16 ? 8 : 4) == 0;
-  return wdtype == EA_BF16 ? launch_fwd_mt<true>(p, (hipStream_t)stream) : launch_fwd_mt<false>(p, (hipStream_t)stream);
+  // a training batch fills 64-row blocks; the narrow row tiles serve B < 64 (the last batch of
+  // an epoch, validation).  Two column tiles per block from H = 1024 up, as ea_lstm_step does.
+  const int ntiles = (H + 3) / 4;
+  const bool bf = wdtype == EA_BF16;
+  return launch_tiles(n, ntiles, ntiles >= 256, p, (hipStream_t)stream, [bf](auto mt, auto nj, auto u) {
+    return bf ? lstm_cell_fwd_kernel<true, mt(), nj(), u()> : lstm_cell_fwd_kernel<false, mt(), nj(), u()>;
+  });
 }
 
 extern "C" int ea_lstm_cell_bwd(int wdtype, int n, int H, const void* wpack_t, const void* dgates_next, long lddn,
@@ -378,5 +181,8 @@ extern "C" int ea_lstm_cell_bwd(int wdtype, int n, int H, const void* wpack_t, c
   p.dho = dh_out; p.lddh = lddh; p.gates = gates; p.ldg = ldg; p.c = c; p.cprev = c_prev; p.ldc = ldc;
   p.dci = dc_in; p.dco = dc_out; p.lddc = lddc; p.dg = dgates; p.dgb = (bf16*)dgates_b; p.ldd = ldd;
   p.dht = dh_tot; p.ldt = ldt;
-  return wdtype == EA_BF16 ? launch_bwd_mt<true>(p, (hipStream_t)stream) : launch_bwd_mt<false>(p, (hipStream_t)stream);
+  const bool bf = wdtype == EA_BF16;
+  return launch_tiles(n, ea_cdiv(H, 16), false, p, (hipStream_t)stream, [bf](auto mt, auto, auto u) {
+    return bf ? lstm_cell_bwd_kernel<true, mt(), u()> : lstm_cell_bwd_kernel<false, mt(), u()>;
+  });
 }

@@ -1,5 +1,4 @@
-"""Training path of SequentialRNNLM: the weight packs of the recurrent step kernels and the
-autograd nodes (embedding, dropout, one node per LSTM layer, the output Linear, the loss).
+"""Training path of SequentialRNNLM: the autograd nodes (embedding, dropout, one node per LSTM layer, the output Linear, the loss).
 
 Rows are time-major inside the path (row t * B + b), so the slice of one time step is a
 contiguous (B, .) block for ea_lstm_cell_fwd / ea_lstm_cell_bwd and every product that is not
@@ -13,69 +12,10 @@ from __future__ import annotations
 import torch
 
 from .. import hip_ops as ops
-from .._lib import BF16, F32, LSTM_KG, lib
+from .._lib import BF16, F32, lib
+from .lstm_pack import rup
 
-KG = LSTM_KG
 EMBED_BWD_ROWS = 4096  # ea_embed_bwd stages the ids of one call in LDS
-
-
-def _rup(x: int, g: int = KG) -> int:
-    return (x + g - 1) // g * g
-
-
-def _slice(dtype) -> int:
-    return 32 if dtype == torch.bfloat16 else 16
-
-
-def pack_lstm_hh(w_hh: torch.Tensor, dtype=torch.float32) -> torch.Tensor:
-    """(4H, H) torch weight_hh -> the flat forward operand of ea_lstm_cell_fwd: element
-    (tile t, slice s, row r = 4 * u + gate, j) at ((t * nks + s) * 16 + r) * SL + j holds
-    weight_hh[gate * H + 4 * t + u, s * SL + j] (0 outside), SL = 16 (f32) / 32 (bf16),
-    nks = Hp / SL, Hp = H rounded up to EA_LSTM_KG."""
-    return HHPacks(w_hh, dtype).refresh(w_hh).fwd.clone()
-
-
-def pack_lstm_hh_t(w_hh: torch.Tensor, dtype=torch.float32) -> torch.Tensor:
-    """(4H, H) torch weight_hh -> the flat backward operand of ea_lstm_cell_bwd (W_hh^T, K = 4H):
-    element (tile t, slice s, row r, j) at ((t * nks + s) * 16 + r) * SL + j holds
-    weight_hh[s * SL + j, 16 * t + r] (0 outside), nks = Gp / SL, Gp = 4H rounded up to
-    EA_LSTM_KG."""
-    return HHPacks(w_hh, dtype).refresh(w_hh).bwd.clone()
-
-
-class HHPacks:
-    """Both packs of one layer's weight_hh with their zero-padded staging buffers, so that
-    refresh() is four strided copies on the current stream: no allocation, no host
-    synchronisation (it runs after every optimizer step)."""
-
-    def __init__(self, w_hh: torch.Tensor, dtype):
-        G, H = w_hh.shape
-        if G != 4 * H:
-            raise ValueError(f"not an LSTM weight_hh: {tuple(w_hh.shape)}")
-        dev = w_hh.device
-        self.H, self.dtype = H, dtype
-        SL = _slice(dtype)
-        Hp, Gp = _rup(H), _rup(G)
-        nt, ntt = (H + 3) // 4, (H + 15) // 16
-        self._stage = torch.zeros(4, nt * 4, Hp, dtype=torch.float32, device=dev)
-        self._stage_t = torch.zeros(ntt * 16, Gp, dtype=torch.float32, device=dev)
-        self.fwd = torch.zeros(nt * (Hp // SL) * 16 * SL, dtype=dtype, device=dev)
-        self.bwd = torch.zeros(ntt * (Gp // SL) * 16 * SL, dtype=dtype, device=dev)
-        # (gate, t, u, s, j) -> (t, s, u, gate, j) and (t, r, s, j) -> (t, s, r, j)
-        self._src = self._stage.view(4, nt, 4, Hp // SL, SL).permute(1, 3, 2, 0, 4)
-        self._dst = self.fwd.view(nt, Hp // SL, 4, 4, SL)
-        self._src_t = self._stage_t.view(ntt, 16, Gp // SL, SL).permute(0, 2, 1, 3)
-        self._dst_t = self.bwd.view(ntt, Gp // SL, 16, SL)
-
-    @torch.no_grad()
-    def refresh(self, w_hh: torch.Tensor):
-        H = self.H
-        w = w_hh.detach()
-        self._stage[:, :H, :H].copy_(w.view(4, H, H))
-        self._dst.copy_(self._src)
-        self._stage_t[:H, :4 * H].copy_(w.t())
-        self._dst_t.copy_(self._src_t)
-        return self
 
 
 def _f32c(t: torch.Tensor) -> torch.Tensor:
@@ -146,7 +86,7 @@ class LSTMLayerFn(torch.autograd.Function):
         bf = lm._cd == torch.bfloat16
         wd = BF16 if bf else F32
         H, dev = lm.nhid, x.device
-        Hp, G = _rup(H), 4 * H
+        Hp, G = rup(H), 4 * H
         st = ops.stream()
         w_ih = lm._w(f"rnn.weight_ih_l{k}")
         bsum = getattr(lm.rnn, f"bias_ih_l{k}").detach() + getattr(lm.rnn, f"bias_hh_l{k}").detach()
@@ -182,8 +122,8 @@ class LSTMLayerFn(torch.autograd.Function):
         bf = lm._cd == torch.bfloat16
         wd = BF16 if bf else F32
         H, dev = lm.nhid, dy.device
-        Hp, G = _rup(H), 4 * H
-        ldd = _rup(G)
+        Hp, G = rup(H), 4 * H
+        ldd = rup(G)
         st = ops.stream()
         dy = _f32c(dy)
         lddy = dy.stride(0)

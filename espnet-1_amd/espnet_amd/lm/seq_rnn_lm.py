@@ -10,7 +10,7 @@ state by index), the output Linear on the few-row GEMM and the row log-softmax: 
 launches.
 
 The kernels read packed copies made in prepare(): the LSTM weights in the slice-major tile
-layout of include/espnet_amd.h (pack_lstm_weights), the embedding table and decoder.weight
+layout of include/espnet_amd.h (lstm_pack.py), the embedding table and decoder.weight
 with their rows zero padded to a multiple of EA_LSTM_KG.  A step's states live in one
 (2, nlayers, n, Hp) buffer; batch_score returns views of it and recognises them when they come
 back, so the beam's reordering costs an index vector and no copy.
@@ -33,46 +33,18 @@ import torch
 from torch import nn
 
 from .. import hip_ops as ops
-from .._lib import BF16, F32, LSTM_KG, lib
+from .._lib import BF16, F32, lib
 from ..arena import ParamArena
 from ..layers.common import site_seed
-from .rnn_train import DropFn, EmbedFn, HHPacks, LSTMLayerFn, OutLinearFn, pack_lstm_hh, pack_lstm_hh_t  # noqa: F401
+from .lstm_pack import HHPacks, pack_lstm_bias, pack_lstm_hh, pack_lstm_hh_t, pack_lstm_weights, rup
+from .rnn_train import DropFn, EmbedFn, LSTMLayerFn, OutLinearFn
 
-KG = LSTM_KG  # K granule of the packed operands
-TILE_UNITS = 4  # hidden units per weight tile (x 4 gates = 16 rows, one MFMA column tile)
-
-
-def _rup(x: int, g: int = KG) -> int:
-    return (x + g - 1) // g * g
-
-
-def pack_lstm_weights(w_ih: torch.Tensor, w_hh: torch.Tensor, dtype=torch.float32) -> torch.Tensor:
-    """(4H, I), (4H, H) torch LSTM weights -> the flat packed operand of ea_lstm_step:
-    element (tile t, slice s, row r = 4 * u + gate, j) at ((t * nks + s) * 16 + r) * SL + j holds
-    [W_ih | 0 | W_hh | 0][gate * H + 4 * t + u, s * SL + j], SL = 16 (f32) / 32 (bf16)."""
-    H, I = w_hh.shape[1], w_ih.shape[1]
-    if w_ih.shape[0] != 4 * H or w_hh.shape[0] != 4 * H:
-        raise ValueError(f"not LSTM weights: {tuple(w_ih.shape)}, {tuple(w_hh.shape)}")
-    Ip, Hp = _rup(I), _rup(H)
-    nt = (H + TILE_UNITS - 1) // TILE_UNITS
-    W = torch.zeros(4, nt * TILE_UNITS, Ip + Hp, dtype=torch.float32, device=w_ih.device)
-    W[:, :H, :I] = w_ih.detach().float().view(4, H, I)
-    W[:, :H, Ip:Ip + H] = w_hh.detach().float().view(4, H, H)
-    SL = 32 if dtype == torch.bfloat16 else 16
-    nks = (Ip + Hp) // SL
-    # (gate, t, u, s, j) -> (t, s, u, gate, j)
-    P = W.view(4, nt, TILE_UNITS, nks, SL).permute(1, 3, 2, 0, 4)
-    return P.to(dtype).contiguous().view(-1)
-
-
-def pack_lstm_bias(b_ih: torch.Tensor, b_hh: torch.Tensor) -> torch.Tensor:
-    """(4H,) + (4H,) -> f32 (4H,) with [4 * unit + gate] = b_ih + b_hh of row gate * H + unit."""
-    H = b_ih.numel() // 4
-    return (b_ih.detach().float() + b_hh.detach().float()).view(4, H).t().contiguous().view(-1)
+# the pack functions stay importable from this module, where callers found them before lstm_pack.py
+__all__ = ["SequentialRNNLM", "HHPacks", "pack_lstm_bias", "pack_lstm_hh", "pack_lstm_hh_t", "pack_lstm_weights"]
 
 
 def _pad_cols(w: torch.Tensor, dtype) -> torch.Tensor:
-    out = torch.zeros(w.shape[0], _rup(w.shape[1]), dtype=dtype, device=w.device)
+    out = torch.zeros(w.shape[0], rup(w.shape[1]), dtype=dtype, device=w.device)
     out[:, :w.shape[1]] = w.detach()
     return out
 
@@ -166,7 +138,7 @@ class SequentialRNNLM(nn.Module):
             self._bias.append(pack_lstm_bias(getattr(self.rnn, f"bias_ih_l{k}"), getattr(self.rnn, f"bias_hh_l{k}")))
         self._wdec = _pad_cols(self.decoder.weight, cd)
         self._bdec = self.decoder.bias.detach().float().contiguous()
-        Hp = _rup(self.nhid)
+        Hp = rup(self.nhid)
         self._zero = torch.zeros(2, self.nlayers, 1, Hp, device=self._device)
         self._src0 = {}
         self._recent.clear()
@@ -271,7 +243,7 @@ class SequentialRNNLM(nn.Module):
         """Fallback: states of mixed origin (None = zeros, (L, H) or (L, 1, H) tensors) copied into
         a fresh (2, L, n, Hp) buffer."""
         L, H = self.nlayers, self.nhid
-        prev = torch.zeros(2, L, len(states), _rup(H), device=self._device)
+        prev = torch.zeros(2, L, len(states), rup(H), device=self._device)
         for i, s in enumerate(states):
             if s is None:
                 continue
@@ -378,7 +350,7 @@ class SequentialRNNLM(nn.Module):
     def _forward(self, input, hidden):
         ids = input.to(self._device, torch.int64).contiguous()
         B, T = ids.shape
-        L, H, Hp = self.nlayers, self.nhid, _rup(self.nhid)
+        L, H, Hp = self.nlayers, self.nhid, rup(self.nhid)
         prev = torch.zeros(2, L, B, Hp, device=self._device)
         if hidden is not None:
             for j in (0, 1):

@@ -839,8 +839,20 @@ int ea_merge_conv_bwd(int B, int T, int C, int K, const void* xc, const void* dm
 
 /* ---------------------------------------------------------------- SequentialRNNLM (decoding) */
 
-/* K granule of the packed LSTM weights: the W_ih and the W_hh part of a row are each zero
- * padded to a multiple of it. */
+/* LSTM weight packs (made by espnet_amd/lm/lstm_pack.py; read by ea_lstm_step, ea_lstm_cell_fwd
+ * and ea_lstm_cell_bwd).  A pack is a zero-padded matrix (tiles * 16 rows, K), K a multiple of
+ * EA_LSTM_KG, stored tile by tile and slice-major inside a tile: with SL = 16 (f32) / 32 (bf16)
+ * elements per slice and nks = K / SL, element (tile t, slice s, row r, j) = M[16t + r, s*SL + j]
+ * is at ((t * nks + s) * 16 + r) * SL + j.  16-B aligned.  The three matrices:
+ *  step pack (ea_lstm_step, pack_lstm_weights): forward tiles of [W_ih | 0 | W_hh | 0].  Ip / Hp =
+ *    I / H rounded up to EA_LSTM_KG, K = Ip + Hp, k-range [0, I) = W_ih, [Ip, Ip + H) = W_hh.  A
+ *    forward tile t holds hidden units 4t .. 4t+3 (units >= H: zero rows), its row 4*u + gate is
+ *    row gate*H + 4t + u of the torch weights.  ceil(H / 4) tiles.
+ *  forward pack (ea_lstm_cell_fwd, pack_lstm_hh): forward tiles of W_hh alone, K = Hp: the slices
+ *    [Ip / SL, (Ip + Hp) / SL) of the step pack's tiles.
+ *  backward pack (ea_lstm_cell_bwd, pack_lstm_hh_t): W_hh^T, K = Gp = 4H rounded up to
+ *    EA_LSTM_KG; tile t holds hidden units 16t .. 16t+15 as its rows, M[16t + r, k] =
+ *    weight_hh[k, 16t + r].  ceil(H / 16) tiles. */
 enum { EA_LSTM_KG = 32 };
 
 /* One LSTM layer over one token of n hypotheses, in one launch (torch.nn.LSTM inside
@@ -848,11 +860,7 @@ enum { EA_LSTM_KG = 32 };
  *   gates = x . W_ih^T + h_prev[src] . W_hh^T + bias     (n, 4H), gate order i, f, g, o
  *   c' = sigmoid(f) * c_prev[src] + sigmoid(i) * tanh(g);   h' = sigmoid(o) * tanh(c')
  * Accumulation, activations and the state are f32.  I and H are any positive integers.
- *  wpack (wdtype EA_F32 / EA_BF16, 16-B aligned): the packed weights.  Ip / Hp = I / H rounded
- *    up to EA_LSTM_KG, K = Ip + Hp, row k-range [0, I) = W_ih, [Ip, Ip + H) = W_hh, the rest 0;
- *    tile t holds hidden units 4t .. 4t+3 (units >= H: zero rows), its row 4*u + gate is row
- *    gate*H + 4t + u of the torch weights; with SL = 16 (f32) / 32 (bf16) and nks = K / SL,
- *    element (tile t, slice s, row r, j) is at ((t * nks + s) * 16 + r) * SL + j.
+ *  wpack (wdtype EA_F32 / EA_BF16): the step pack (LSTM weight packs above).
  *    EA_BF16: x and h_prev are rounded to bf16 for the product (f32 accumulation).
  *  bias (f32, 4H, 16-B aligned): bias[4 * unit + gate] = b_ih + b_hh of that gate row.
  *  x (n rows, ldx >= I); with tok != NULL x is the embedding table (V rows, ldx) and row r
@@ -877,14 +885,7 @@ int ea_lstm_step(int wdtype, int n, int I, int H, const void* wpack, const float
  * Accumulation, activations, states and gradients are f32; wdtype EA_BF16 multiplies bf16
  * operands (the pack and a bf16 h / dgates).  H is any positive integer, n >= 0 (0: no launch).
  *
- * Packs (16-B aligned, SL = 16 (f32) / 32 (bf16) elements per slice, zero filled):
- *  pack_lstm_hh   (forward): the W_hh part of ea_lstm_step's pack on its own.  K = Hp = H rounded
- *    up to EA_LSTM_KG, nks = Hp / SL; tile t holds hidden units 4t .. 4t+3, its row 4*u + gate is
- *    row gate*H + 4t + u of weight_hh; element (t, s, r, j) at ((t * nks + s) * 16 + r) * SL + j
- *    = weight_hh[gate*H + 4t + u, s * SL + j].  ceil(H / 4) tiles.
- *  pack_lstm_hh_t (backward): the transpose.  K = Gp = 4H rounded up to EA_LSTM_KG, nks = Gp / SL;
- *    tile t holds hidden units 16t .. 16t+15 as its rows; element (t, s, r, j) at the same address
- *    formula = weight_hh[s * SL + j, 16t + r].  ceil(H / 16) tiles.
+ * wpack / wpack_t: the forward / backward pack of weight_hh (LSTM weight packs above).
  *
  * ea_lstm_cell_fwd:  gates = xproj + h_prev . W_hh^T (gate order i, f, g, o);
  *   c = sigmoid(f) c_prev + sigmoid(i) tanh(g);  h = sigmoid(o) tanh(c)

@@ -29,7 +29,7 @@ INFINITY_CACHE = 256 * 2 ** 20
 
 
 def kernel_name(unit, n, amp):
-    """The ea_lstm_step instantiation a configuration launches (csrc/rnn_lm.hip launch_lstm_mt)."""
+    """The ea_lstm_step instantiation a configuration launches (csrc/lstm_core.h launch_tiles)."""
     mt = 1 if n <= 16 else 2 if n <= 32 else 4
     nj = 2 if (unit + 3) // 4 >= 256 else 1
     return f"lstm_step_kernel<{'true' if amp else 'false'}, {mt}, {nj}, {4 if mt == 4 else 8}>"

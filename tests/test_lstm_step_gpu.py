@@ -1,6 +1,7 @@
 """ea_lstm_step (csrc/rnn_lm.hip) through the C ABI alone against a float64 restatement,
 element-wise: arbitrary I / H (1, not a multiple of 8, below a tile, the recipes' 650, the
-deepest K split), row counts on both sides of every row-tile choice (1, 3 | 16 | 17 | 61), both
+deepest K split), row counts on both sides of every row-tile choice (1, 3 | 16 | 17 | 61, and 65,
+a second block row, at two small shapes), both
 packed operand types, the parent gather (none, a permutation, one parent for every row, the
 last with the token-id / embedding-table form of x), aligned and unaligned operand strides
 (the 16-B and the element-wise operand loads), NaN-prefilled outputs with a row stride > H.
@@ -24,7 +25,7 @@ _CACHE = {}
 def _weights(I, H):
     """torch's LSTM init, uniform(+-1/sqrt(H)) (no gate saturates); packs made once per shape."""
     if (I, H) not in _CACHE:
-        from espnet_amd.lm.seq_rnn_lm import pack_lstm_bias, pack_lstm_weights
+        from espnet_amd.lm.lstm_pack import pack_lstm_bias, pack_lstm_weights
         g = torch.Generator().manual_seed(17 * I + H)
         k = 1.0 / math.sqrt(H)
         w_ih, w_hh = [(torch.rand(4 * H, i, generator=g) * 2 - 1) * k for i in (I, H)]
@@ -53,6 +54,17 @@ def _strided(t, ld, rows=None, fill=0.0):
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
 @pytest.mark.parametrize("I,H", SHAPES)
 def test_lstm_step_against_float64(I, H, dtype, n):
+    _check_step(I, H, dtype, n)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+@pytest.mark.parametrize("I,H", [(5, 3), (26, 26)])
+def test_lstm_step_second_block_row_against_float64(I, H, dtype):
+    """n = 65: grid.y = 2, the second block row holds one hypothesis (the small shapes only)."""
+    _check_step(I, H, dtype, 65)
+
+
+def _check_step(I, H, dtype, n):
     from espnet_amd import hip_ops as ops
     from espnet_amd._lib import BF16, F32, lib
     w_ih, w_hh, b_ih, b_hh, packs, bias = _weights(I, H)
@@ -112,7 +124,7 @@ def test_lstm_step_against_float64(I, H, dtype, n):
 
 def test_lstm_step_rejects_bad_arguments():
     from espnet_amd._lib import F32, HipError, lib
-    from espnet_amd.lm.seq_rnn_lm import pack_lstm_bias, pack_lstm_weights
+    from espnet_amd.lm.lstm_pack import pack_lstm_bias, pack_lstm_weights
     H = 4
     w = pack_lstm_weights(torch.zeros(16, 4), torch.zeros(16, 4)).cuda()
     b = pack_lstm_bias(torch.zeros(16), torch.zeros(16)).cuda()

@@ -88,7 +88,7 @@ def _put(t, ld):
 
 def test_pack_round_trip_cpu():
     """Every weight_hh element sits at the documented address of both packs, the rest is 0."""
-    from espnet_amd.lm.seq_rnn_lm import pack_lstm_hh, pack_lstm_hh_t
+    from espnet_amd.lm.lstm_pack import pack_lstm_hh, pack_lstm_hh_t
     for H in (3, 26, 64):
         w = _w_hh(H)
         for dtype, SL in ((torch.float32, 16), (torch.bfloat16, 32)):
@@ -121,7 +121,7 @@ def test_pack_round_trip_cpu():
 def test_cell_fwd_bwd_against_float64(H, B, T, dtype):
     from espnet_amd import hip_ops as ops
     from espnet_amd._lib import BF16, F32, lib
-    from espnet_amd.lm.seq_rnn_lm import pack_lstm_hh, pack_lstm_hh_t
+    from espnet_amd.lm.lstm_pack import pack_lstm_hh, pack_lstm_hh_t
     bf = dtype == torch.bfloat16
     wd = BF16 if bf else F32
     w = _w_hh(H)
@@ -197,7 +197,7 @@ def test_argument_checks():
     return the error code before anything is launched; n = 0 is a no-op."""
     from espnet_amd import hip_ops as ops
     from espnet_amd._lib import F32, HipError, lib
-    from espnet_amd.lm.seq_rnn_lm import pack_lstm_hh, pack_lstm_hh_t
+    from espnet_amd.lm.lstm_pack import pack_lstm_hh, pack_lstm_hh_t
     H, B = 8, 4
     G, Hp = 4 * H, 32
     w = _w_hh(H).cuda()

@@ -107,7 +107,7 @@ def _packed_gemv(P, I, H, SL, x, h):
 @pytest.mark.parametrize("I,H", [(1, 1), (5, 3), (26, 26), (24, 40), (650, 650)])
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_pack_layout_against_numpy(I, H, dtype):
-    from espnet_amd.lm.seq_rnn_lm import pack_lstm_bias, pack_lstm_weights
+    from espnet_amd.lm.lstm_pack import pack_lstm_bias, pack_lstm_weights
     g = torch.Generator().manual_seed(I * 1000 + H)
     w_ih = torch.randint(-3, 4, (4 * H, I), generator=g).float()  # integers: exact in bf16 and in any sum order
     w_hh = torch.randint(-3, 4, (4 * H, H), generator=g).float()
@@ -126,3 +126,26 @@ def test_pack_layout_against_numpy(I, H, dtype):
     b_ih, b_hh = torch.arange(4 * H).float(), 100.0 * torch.arange(4 * H).float()
     pb = pack_lstm_bias(b_ih, b_hh)
     assert torch.equal(pb.view(H, 4).t().reshape(-1), b_ih + b_hh)
+
+
+@pytest.mark.parametrize("I", [1, 40])
+@pytest.mark.parametrize("H", [3, 26, 64])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+def test_step_pack_holds_the_hh_pack_and_refresh_leaves_nothing_stale(H, I, dtype):
+    """The K slices [Ip / SL, (Ip + Hp) / SL) of every tile of the decoding step's pack are the
+    training forward's pack bit for bit, and an HHPacks refreshed with other weights equals a
+    fresh pack of those weights in both operands."""
+    from espnet_amd.lm.lstm_pack import HHPacks, pack_lstm_hh, pack_lstm_hh_t, pack_lstm_weights
+    g = torch.Generator().manual_seed(100 * H + I)
+    w_ih, w_hh, w2 = torch.randn(4 * H, I, generator=g), torch.randn(4 * H, H, generator=g), torch.randn(4 * H, H, generator=g)
+    SL = 32 if dtype == torch.bfloat16 else 16
+    bits = torch.int16 if dtype == torch.bfloat16 else torch.int32
+    Ip, Hp, nt = (I + 31) // 32 * 32, (H + 31) // 32 * 32, (H + 3) // 4
+    full = pack_lstm_weights(w_ih, w_hh, dtype).view(nt, (Ip + Hp) // SL, 16 * SL)
+    hh = pack_lstm_hh(w_hh, dtype).view(nt, Hp // SL, 16 * SL)
+    assert torch.equal(full[:, Ip // SL:].view(bits), hh.view(bits))
+    packs = HHPacks(w_hh, dtype).refresh(w_hh)
+    assert torch.equal(packs.fwd.view(bits), hh.reshape(-1).view(bits))
+    packs.refresh(w2)
+    assert torch.equal(packs.fwd.view(bits), pack_lstm_hh(w2, dtype).view(bits))
+    assert torch.equal(packs.bwd.view(bits), pack_lstm_hh_t(w2, dtype).view(bits))
