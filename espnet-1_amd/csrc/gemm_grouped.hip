@@ -19,8 +19,9 @@ struct GroupProbD {
   int M, N, K;
   int tiles_n, tile0;
   float beta;
+  float* a_sum;  // [M] (+)= K-sums of the A rows, written by the problem's tn == 0 tiles; or null
 };
-constexpr int EA_GROUP_CHUNK = 60;
+constexpr int EA_GROUP_CHUNK = 55;
 struct GroupChunk {
   int first, n;  // problems [first, first + n) of the table
   GroupProbD pr[EA_GROUP_CHUNK];
@@ -79,7 +80,27 @@ __global__ __launch_bounds__(512, 1) void gemm_grouped(const GroupProbD* __restr
   for (int i = 0; i < 8; ++i)
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  pipe_tile<AK, BKM, 0, 256, NS>(p, tile_ov(p), smem, q.A, q.B, m0, n0, 0, q.K, acc);
+  // bias gradients from the weight-gradient GEMM's dY operand: the first N tile of each tile
+  // row also sums its A rows over K (block-uniform: one dispatch, no branch in the K loop)
+  if (q.a_sum != nullptr && tn == 0) {
+    f32x4 asum[2] = {(f32x4){0.f, 0.f, 0.f, 0.f}, (f32x4){0.f, 0.f, 0.f, 0.f}};
+    pipe_tile<AK, BKM, 0, 256, NS, true>(p, tile_ov(p), smem, q.A, q.B, m0, n0, 0, q.K, acc, asum);
+    if ((lane & 15) == 0) {  // column 0 of the 16 x 16 blocks: rows (lane >> 4) * 4 + r
+#pragma unroll
+      for (int e = 0; e < 2; ++e)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int m = m0 + wm + ((w & 3) * 2 + e) * 16 + (lane >> 4) * 4 + r;
+          if (m < q.M) {  // rows past M are clamped duplicates of row M - 1
+            float v = asum[e][r];
+            if (q.beta != 0.f) v += q.beta * q.a_sum[m];
+            q.a_sum[m] = v;
+          }
+        }
+    }
+  } else {
+    pipe_tile<AK, BKM, 0, 256, NS>(p, tile_ov(p), smem, q.A, q.B, m0, n0, 0, q.K, acc);
+  }
   const EpiK ek = make_epik(p);
   epi_wave<EA_EPI_STORE, 8, 4>(p, ek, smem, 0, 0, 0, m0 + wm, n0 + wn, lane, w, acc);
 }
@@ -124,6 +145,20 @@ extern "C" int ea_gemm_grouped(int a_kmajor, int b_kmajor, int n, const ea_group
     const double b_ext = 2.0 * ((b_kmajor ? (double)e.N : (double)e.K) * e.ldb);
     EA_CHECK_ARG(a_ext < 4.0e9 && b_ext < 4.0e9);
     ntiles += (long)ea_cdiv(e.M, 256) * ea_cdiv(e.N, 256);
+    if (e.a_sum) {  // written beside every C of the launch: no overlap with any C or other a_sum
+      EA_CHECK_ARG(((uintptr_t)e.a_sum % 4) == 0);
+      const uintptr_t lo = (uintptr_t)e.a_sum, hi = lo + 4 * (uintptr_t)e.M;
+      for (int j = 0; j < n; ++j) {
+        const ea_group_gemm& o = probs[j];
+        if (!o.C || o.M <= 0 || o.N <= 0) continue;  // refused at its own turn
+        const uintptr_t clo = (uintptr_t)o.C, chi = clo + 4 * ((uintptr_t)(o.M - 1) * o.ldc + o.N);
+        EA_CHECK_ARG(!(lo < chi && clo < hi));
+        if (j != i && o.a_sum) {
+          const uintptr_t slo = (uintptr_t)o.a_sum;
+          EA_CHECK_ARG(!(lo < slo + 4 * (uintptr_t)o.M && slo < hi));
+        }
+      }
+    }
   }
   EA_CHECK_ARG(ntiles < (1L << 30) && grouped_ws_bytes(n, ntiles) <= ws_bytes);
   GroupProbD* table = (GroupProbD*)ws;
@@ -139,6 +174,7 @@ extern "C" int ea_gemm_grouped(int a_kmajor, int b_kmajor, int n, const ea_group
     d.tiles_n = ea_cdiv(e.N, 256);
     d.tile0 = tile0;
     d.beta = e.beta;
+    d.a_sum = e.a_sum;
     tile0 += ea_cdiv(e.M, 256) * d.tiles_n;
     if (c.n == EA_GROUP_CHUNK || i == n - 1) {
       hipLaunchKernelGGL(group_upload, dim3(1), dim3(256), 0, st, c, table, map);

@@ -1369,12 +1369,17 @@ EA_DEV TileOv tile_ov(const GemmP& p) { return TileOv{p.M, p.g.a, p.g.e, p.w1par
 
 // One BT x BT output tile over K range [kbeg, kend) into acc (the wave's sub-tile, PipeT);
 // A / B point at this tile's batch slice.  Returns with every wave done reading smem.
-template <bool AK, bool BKM, int MODE = 0, int BT = 256, int NS = 4>
+// ASUM (gemm_grouped only): the tile also sums its A rows over K.  Per slice, wave w multiplies
+// the two A fragments 2j, 2j+1 (j = w & 3; the four waves sharing wm hold the same eight) with
+// an all-ones B fragment into asum[0..1]: every column of asum[e] is the K-sum of A rows
+// wm + (2j+e)*16 .. +15, accumulated in the slice order of acc.
+template <bool AK, bool BKM, int MODE = 0, int BT = 256, int NS = 4, bool ASUM = false>
 EA_DEV void pipe_tile(const GemmP& p, const TileOv& ov, char* smem, const bf16* A, const bf16* B, int m0, int n0, int kbeg,
-                      int kend, f32x4 (&acc)[PipeT<BT, NS>::MI][4]) {
+                      int kend, f32x4 (&acc)[PipeT<BT, NS>::MI][4], f32x4* asum = nullptr) {
   static_assert(MODE == 0 || (MODE == EA_CONV_FWD && AK && BKM) || (MODE == EA_CONV_DGRAD && AK) ||
                 (MODE == EA_CONV_WGRAD && !AK && !BKM), "conv gather layouts");
   static_assert(MODE == 0 || BT == 256, "conv gathers run on 256-wide tiles");
+  static_assert(!ASUM || (MODE == 0 && BT == 256), "A row sums: plain 256-wide tiles");
   using PC = PipeT<BT, NS>;
   constexpr int BK = PC::BK, NSLOT = PC::NSLOT, NW = PC::NW, NTT = PC::NTT, MI = PC::MI;
   constexpr int A_BYTES = PC::A_BYTES, B_BYTES = PC::B_BYTES, SLOT = PC::SLOT;
@@ -1547,6 +1552,22 @@ EA_DEV void pipe_tile(const GemmP& p, const TileOv& ov, char* smem, const bf16* 
   lds_barrier();
   if (g1) lds_barrier();  // the stagger
   bf16x8 fa[MI], fb[4];
+  // ASUM: the wave's two fragments picked by wave-uniform selects (a run-time index into fa
+  // would spill it), multiplied with a B fragment of ones
+  auto a_rowsum = [&]() {
+    if constexpr (ASUM) {
+      const int sj = w & 3;
+      bf16x8 ones;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) ones[e] = (bf16)1.f;
+      // by value: ?: on the array's lvalues would select an address and keep fa in memory
+      auto pick = [](bool c, bf16x8 a, bf16x8 b) { return c ? a : b; };
+      const bf16x8 s0 = pick(sj == 0, fa[0], pick(sj == 1, fa[2], pick(sj == 2, fa[4], fa[6])));
+      const bf16x8 s1 = pick(sj == 0, fa[1], pick(sj == 1, fa[3], pick(sj == 2, fa[5], fa[7])));
+      asum[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(s0, ones, asum[0], 0, 0, 0);
+      asum[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(s1, ones, asum[1], 0, 0, 0);
+    }
+  };
   for (int sl = 0; sl < nsl; ++sl) {
     // ---- LOAD(sl)
     __builtin_amdgcn_sched_barrier(0);
@@ -1576,6 +1597,7 @@ EA_DEV void pipe_tile(const GemmP& p, const TileOv& ov, char* smem, const bf16* 
 #pragma unroll
       for (int j = 0; j < 4; ++j)
         acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
+    a_rowsum();
     __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_sched_barrier(0);
     lds_barrier();
@@ -1625,6 +1647,7 @@ EA_DEV void pipe_tile(const GemmP& p, const TileOv& ov, char* smem, const bf16* 
 #pragma unroll
       for (int j = 0; j < 4; ++j)
         acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
+    a_rowsum();  // the zero fill adds nothing
   }
 
   __syncthreads();  // every wave is done reading the ring

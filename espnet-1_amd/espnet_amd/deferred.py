@@ -16,6 +16,9 @@ from .streams import WGRAD, on_side, scratch, stream
 GRAD_READY = None  # callable(prefix): a block's parameter gradients are final (DP overlap)
 
 DEFER_WGRAD = os.environ.get("EA_DEFER_WGRAD", "1") != "0"
+# Linear bias gradients from the deferred weight-gradient GEMM's dY operand (ea_group_gemm.a_sum)
+# instead of a separate column-sum pass over dY; EA_WGRAD_BIAS=0 restores the column sums (A/B)
+WGRAD_BIAS = os.environ.get("EA_WGRAD_BIAS", "1") != "0"
 # bytes the deferred queues may keep alive (queued operands / partial buffers) before they
 # flush early: a pass whose queued dY / X / LayerNorm partials exceed it launches what it has
 # and continues (C3 queues ~3.5 GB per backward, under the default)
@@ -46,7 +49,12 @@ class WgradQueue:
         # per-block joins)
         self.side_events = []
 
-    def add(self, dy, x, dw, *, M, N, K, lda, ldb, ldc, beta, post=None) -> bool:
+    def add(self, dy, x, dw, *, M, N, K, lda, ldb, ldc, beta, post=None, db=None, db_beta=None):
+        """-> False (not queued), True (queued) or "db" (queued, and the launch also writes
+        db (+)= the column sums of dy, as the problem's a_sum).  db is not carried — the caller
+        sums it separately — when WGRAD_BIAS is off, when it does not share dw's accumulate,
+        or when its span overlaps an output REDUCE_Q has claimed (the two queues flush on
+        different streams at the end of the pass)."""
         if not (dy.dtype == torch.bfloat16 and x.dtype == torch.bfloat16 and dw.dtype == torch.float32):
             return False
         if (lda % 8 or ldb % 8 or dy.data_ptr() % 16 or x.data_ptr() % 16 or N % 4 or ldc % 4
@@ -56,19 +64,31 @@ class WgradQueue:
             return False
         lo = dw.data_ptr()
         hi = lo + ((M - 1) * ldc + N) * 4
-        if any(lo < it[-1] and it[-2] < hi for it in self.items):
+        spans = [(lo, hi)]
+        if (db is not None and WGRAD_BIAS and db_beta == beta and db.dtype == torch.float32 and db.is_contiguous()
+                and db.numel() == M and db.data_ptr() % 4 == 0):
+            blo = db.data_ptr()
+            bhi = blo + 4 * M
+            if not (blo < hi and lo < bhi) and not REDUCE_Q.claimed(blo, bhi):
+                spans.append((blo, bhi))
+        if any(l_ < s[1] and s[0] < h for it in self.items for s in it[-1] for l_, h in spans):
             self.flush()
         if on_side():
             ev = torch.cuda.Event()
             ev.record()
             self.side_events.append(ev)
-        self.items.append((K, dy, x, dw, M, N, lda, ldb, ldc, beta, lo, hi))
+        fused = db if len(spans) > 1 else None
+        self.items.append((K, dy, x, dw, M, N, lda, ldb, ldc, beta, fused, spans))
         if post is not None:
             self.posts.append(post)
         self.pending += _nbytes(dy) + _nbytes(x)
         if self.pending > DEFER_BUDGET:
             self.flush()
-        return True
+        return "db" if fused is not None else True
+
+    def carries(self, lo, hi) -> bool:
+        """Does a queued problem write a bias gradient (a_sum) overlapping bytes [lo, hi)?"""
+        return any(lo < s[1] and s[0] < hi for it in self.items for s in it[-1][1:])
 
     def flush(self):
         """Launch the queued GEMMs on the current stream."""
@@ -92,8 +112,9 @@ class WgradQueue:
                 t.record_stream(cur)
         arr = (GroupGemm * n)()
         ntiles = 0
-        for i, (K, dy, x, dw, M, N, lda, ldb, ldc, beta, _, _) in enumerate(items):
-            arr[i] = GroupGemm(dy.data_ptr(), x.data_ptr(), dw.data_ptr(), lda, ldb, ldc, M, N, K, beta)
+        for i, (K, dy, x, dw, M, N, lda, ldb, ldc, beta, db, _) in enumerate(items):
+            arr[i] = GroupGemm(dy.data_ptr(), x.data_ptr(), dw.data_ptr(), lda, ldb, ldc, M, N, K, beta,
+                               None if db is None else db.data_ptr())
             ntiles += ((M + 255) // 256) * ((N + 255) // 256)
         nbytes = ctypes.c_long(0)
         lib.ea_gemm_grouped_ws_bytes(n, ntiles, ctypes.addressof(nbytes))
@@ -132,11 +153,16 @@ class ReduceQueue:
         if self.pending > DEFER_BUDGET:
             self.flush()
 
+    def claimed(self, lo, hi) -> bool:
+        return any(lo < h and l_ < hi for l_, h in self.spans)
+
     def _claim(self, out, n):
         lo = out.data_ptr()
         hi = lo + 4 * n
-        if any(lo < h and l_ < hi for l_, h in self.spans):
+        if self.claimed(lo, hi):
             self.flush()
+        if WGRAD_Q.carries(lo, hi):  # a queued weight-gradient problem writes this bias: it goes first
+            WGRAD_Q.flush()
         self.spans.append((lo, hi))
 
     def add_colsum(self, x, rows, n, ld, out, accumulate) -> bool:

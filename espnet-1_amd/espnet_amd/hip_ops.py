@@ -319,18 +319,24 @@ def linear_dx(dy, w, out, *, epi: Epilogue = None):
                 ldc=ldc, epi=epi)
 
 
-def linear_dw(dy, x, dw, *, accumulate=False, post=None):
+def linear_dw(dy, x, dw, *, accumulate=False, post=None, db=None, db_accumulate=True):
     """dw[n, k] (+)= sum_r dy[r, n] * x[r, k] — Linear weight gradient (f32 out).  While the
     weight-gradient queue is active (a training backward pass) the GEMM is deferred and
     launched with the others of the pass by WGRAD_Q.flush(); `post` (a callable consuming dw,
-    e.g. a permute into the gradient arena) then runs right after that launch."""
+    e.g. a permute into the gradient arena) then runs right after that launch.
+    db: the Linear's bias gradient, db (+)= column sums of dy (db_accumulate, colsum's default).
+    The queued GEMM sums it from its dy operand (ea_group_gemm.a_sum) when it can; otherwise —
+    queue off or problem not taken, f32 dy, EA_WGRAD_BIAS=0 — colsum(dy, db) runs as before."""
     R, N, lddy = _rows(dy)
     R2, K, ldx = _rows(x)
     if R != R2:
         raise HipError("row mismatch in linear_dw")
     beta = 1.0 if accumulate else 0.0
-    if WGRAD_Q.active and WGRAD_Q.add(dy, x, dw, M=N, N=K, K=R, lda=lddy, ldb=ldx, ldc=dw.stride(0), beta=beta,
-                                      post=post):
+    took = WGRAD_Q.active and WGRAD_Q.add(dy, x, dw, M=N, N=K, K=R, lda=lddy, ldb=ldx, ldc=dw.stride(0), beta=beta,
+                                          post=post, db=db, db_beta=1.0 if db_accumulate else 0.0)
+    if db is not None and took != "db":
+        colsum(dy, db, accumulate=db_accumulate)
+    if took:
         return dw
     gemm(dy, x, dw, M=N, N=K, K=R, a_kmajor=0, b_kmajor=0, lda=lddy, ldb=ldx,
          ldc=dw.stride(0), epi=make_epi(beta=beta))

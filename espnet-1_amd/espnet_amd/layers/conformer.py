@@ -177,8 +177,8 @@ def _ffn_bwd(L, b, dx, x_in, saved, pre, ln_name, p, seed_in, seed_out, dv_in=No
     ops.linear_dx(dv, b.w(pre + ".w_2.weight"), dh,
                   epi=ops.make_epi(EPI_DACT, act=ACT_SWISH, aux=h, drop_p=p, seed=seed_in))
     with ops.wgrad(dh, xn):
-        ops.colsum(dh, b.g(pre + ".w_1.bias"))
-        ops.linear_dw(dh, xn, b.g(pre + ".w_1.weight"), accumulate=True)
+        ops.linear_dw(dh, xn, b.g(pre + ".w_1.weight"), accumulate=True,
+                      db=b.g(pre + ".w_1.bias"))
     dxn = empty(N, d, dtype=cd, device=dx.device)
     ops.linear_dx(dh, b.w(pre + ".w_1.weight"), dxn)
     ln_bwd(dxn, x_in, b, ln_name, mu, rs, dx, accumulate=True, drop=next_drop)
@@ -372,8 +372,8 @@ class ConformerBlockFn(torch.autograd.Function):
                               b.g(C + "depthwise_conv.bias").data_ptr(), 1, w, wn, ops.stream())
             lib.ea_glu_bwd(N, d, g2.data_ptr(), ops.dt(g2), dglu.data_ptr(), dg2.data_ptr(), ops.stream())
         with ops.wgrad(dg2, xn3):
-            ops.colsum(dg2, b.g(C + "pointwise_conv1.bias"))
-            ops.linear_dw(dg2, xn3, b.g(C + "pointwise_conv1.weight", shape=(2 * d, d)), accumulate=True)
+            ops.linear_dw(dg2, xn3, b.g(C + "pointwise_conv1.weight", shape=(2 * d, d)), accumulate=True,
+                          db=b.g(C + "pointwise_conv1.bias"))
         dxn3 = empty(N, d, dtype=cd, device=dev)
         ops.linear_dx(dg2, b.w(C + "pointwise_conv1.weight", shape=(2 * d, d)), dxn3)
         dv_att = dv_buf(N, d, cd, dev)
@@ -461,9 +461,9 @@ class ConformerBlockFn(torch.autograd.Function):
         if fork is None:
             dpp_wgrad()
         with ops.wgrad(dqkv, xn2):
-            ops.colsum(dqkv, b.g(A + "linear_q.bias", A + "linear_k.bias", A + "linear_v.bias", shape=(3 * d,)))
             ops.linear_dw(dqkv, xn2, b.g(A + "linear_q.weight", A + "linear_k.weight", A + "linear_v.weight",
-                                          shape=(3 * d, d)), accumulate=True)
+                                          shape=(3 * d, d)), accumulate=True,
+                          db=b.g(A + "linear_q.bias", A + "linear_k.bias", A + "linear_v.bias", shape=(3 * d,)))
         dxn2 = empty(N, d, dtype=cd, device=dev)
         ops.linear_dx(dqkv, qkv_w, dxn2)
         if fork is not None:  # the side GEMM issued after the main chain's next kernel (fork_event)

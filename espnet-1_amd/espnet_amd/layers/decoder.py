@@ -222,8 +222,8 @@ class DecoderFn(torch.autograd.Function):
         dev = dlogits.device
         dlog = ops.cast(dlogits.reshape(N, V).contiguous(), cd)
         with ops.wgrad(dlog, xf):
-            ops.colsum(dlog, b.g("output_layer.bias"))
-            ops.linear_dw(dlog, xf, b.g("output_layer.weight"), accumulate=True)
+            ops.linear_dw(dlog, xf, b.g("output_layer.weight"), accumulate=True,
+                          db=b.g("output_layer.bias"))
         dxf = empty(N, d, dtype=cd, device=dev)
         ops.linear_dx(dlog, b.w("output_layer.weight"), dxf)
         dx = empty(N, d, device=dev)
@@ -253,8 +253,8 @@ class DecoderFn(torch.autograd.Function):
             if fork is not None:
                 ops.flush_wgrad_side(after=fork)
             with ops.wgrad(dh, xn3):
-                ops.colsum(dh, b.g(ff + "w_1.bias"))
-                ops.linear_dw(dh, xn3, b.g(ff + "w_1.weight"), accumulate=True)
+                ops.linear_dw(dh, xn3, b.g(ff + "w_1.weight"), accumulate=True,
+                              db=b.g(ff + "w_1.bias"))
             dxn = empty(N, d, dtype=cd, device=dev)
             ops.linear_dx(dh, b.w(ff + "w_1.weight"), dxn)
             dv_src = dv_buf(N, d, cd, dev)
@@ -273,8 +273,8 @@ class DecoderFn(torch.autograd.Function):
                      seed=sd(l, 3), cd=cd, dq=dq, lddq=d, dk_=dkv[:, 2 * d * l:], lddk=ldkv,
                      dv=dkv[:, 2 * d * l + d:], lddv=ldkv)
             with ops.wgrad(dq, xn2):
-                ops.colsum(dq, b.g(xa + "linear_q.bias"))
-                ops.linear_dw(dq, xn2, b.g(xa + "linear_q.weight"), accumulate=True)
+                ops.linear_dw(dq, xn2, b.g(xa + "linear_q.weight"), accumulate=True,
+                              db=b.g(xa + "linear_q.bias"))
             dxn = empty(N, d, dtype=cd, device=dev)
             ops.linear_dx(dq, b.w(xa + "linear_q.weight"), dxn)
             dv_self = dv_buf(N, d, cd, dev)
@@ -295,8 +295,8 @@ class DecoderFn(torch.autograd.Function):
             wn = (sa + "linear_q.weight", sa + "linear_k.weight", sa + "linear_v.weight")
             bn = (sa + "linear_q.bias", sa + "linear_k.bias", sa + "linear_v.bias")
             with ops.wgrad(dqkv, xn1):
-                ops.colsum(dqkv, b.g(*bn, shape=(3 * d,)))
-                ops.linear_dw(dqkv, xn1, b.g(*wn, shape=(3 * d, d)), accumulate=True)
+                ops.linear_dw(dqkv, xn1, b.g(*wn, shape=(3 * d, d)), accumulate=True,
+                              db=b.g(*bn, shape=(3 * d,)))
             dxn = empty(N, d, dtype=cd, device=dev)
             ops.linear_dx(dqkv, b.w(*wn, shape=(3 * d, d)), dxn)
             dv_ff = dv_buf(N, d, cd, dev) if l > 0 else None  # layer l-1's feed-forward site
@@ -308,8 +308,8 @@ class DecoderFn(torch.autograd.Function):
                          b.g("embed.0.weight").data_ptr(), ops.stream())
         kvw, kvb = _kv_names(nb)
         with ops.wgrad(dkv, mem):
-            ops.colsum(dkv, b.g(*kvb, shape=(ldkv,)))
-            ops.linear_dw(dkv, mem, b.g(*kvw, shape=(ldkv, d)), accumulate=True)
+            ops.linear_dw(dkv, mem, b.g(*kvw, shape=(ldkv, d)), accumulate=True,
+                          db=b.g(*kvb, shape=(ldkv,)))
         dmem = empty(Nm, d, device=dev)
         ops.linear_dx(dkv, b.w(*kvw, shape=(ldkv, d)), dmem)
         ops.grad_ready(b)

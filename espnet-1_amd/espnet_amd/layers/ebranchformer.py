@@ -206,9 +206,9 @@ def _attn_bwd(L, b, dO, xn, O, saved, pos, olens, B, T, pa, seed3):
     if fork is None:
         dpp_wgrad()
     with ops.wgrad(dqkv, xn):
-        ops.colsum(dqkv, b.g(A + "linear_q.bias", A + "linear_k.bias", A + "linear_v.bias", shape=(3 * d,)))
         ops.linear_dw(dqkv, xn, b.g(A + "linear_q.weight", A + "linear_k.weight", A + "linear_v.weight",
-                                    shape=(3 * d, d)), accumulate=True)
+                                    shape=(3 * d, d)), accumulate=True,
+                      db=b.g(A + "linear_q.bias", A + "linear_k.bias", A + "linear_v.bias", shape=(3 * d,)))
     dxn = empty(N, d, dtype=cd, device=dev)
     ops.linear_dx(dqkv, qkv_w, dxn)
     if fork is not None:  # the side GEMM issued after the main chain's next kernel (fork_event)
@@ -327,8 +327,8 @@ class EBranchformerBlockFn(torch.autograd.Function):
         xnm, mum, rsm, h, gmu, grs, gout = s_mlp
         dv2 = dxc[:, d:]
         with ops.wgrad(dxc, gout):
-            ops.colsum(dv2, b.g(G + "channel_proj2.bias"))
-            ops.linear_dw(dv2, gout, b.g(G + "channel_proj2.weight"), accumulate=True)
+            ops.linear_dw(dv2, gout, b.g(G + "channel_proj2.weight"), accumulate=True,
+                          db=b.g(G + "channel_proj2.bias"))
         dgout = empty(N, C, dtype=cd, device=dev)
         ops.linear_dx(dv2, b.w(G + "channel_proj2.weight"), dgout)
         n_dln, n_ws = _long(), _long()
@@ -345,8 +345,8 @@ class EBranchformerBlockFn(torch.autograd.Function):
                         dln.data_ptr(), w, wn, ops.stream())
         del dln, dgout
         with ops.wgrad(dh, xnm):
-            ops.colsum(dh, b.g(G + "channel_proj1.0.bias"))
-            ops.linear_dw(dh, xnm, b.g(G + "channel_proj1.0.weight"), accumulate=True)
+            ops.linear_dw(dh, xnm, b.g(G + "channel_proj1.0.weight"), accumulate=True,
+                          db=b.g(G + "channel_proj1.0.bias"))
         dxnm = empty(N, d, dtype=cd, device=dev)
         ops.linear_dx(dh, b.w(G + "channel_proj1.0.weight"), dxnm)
         ln_bwd(dxnm, x1, b, "norm_mlp", mum, rsm, dx, accumulate=True)
@@ -354,8 +354,8 @@ class EBranchformerBlockFn(torch.autograd.Function):
         xna, mua, rsa, O, s_core = s_att
         dv1 = dxc[:, :d]
         with ops.wgrad(dxc, O):
-            ops.colsum(dv1, b.g("attn.linear_out.bias"))
-            ops.linear_dw(dv1, O, b.g("attn.linear_out.weight"), accumulate=True)
+            ops.linear_dw(dv1, O, b.g("attn.linear_out.weight"), accumulate=True,
+                          db=b.g("attn.linear_out.bias"))
         dO = empty(N, d, dtype=cd, device=dev)
         ops.linear_dx(dv1, b.w("attn.linear_out.weight"), dO)
         dxna = _attn_bwd(L, b, dO, xna, O, s_core, pos, olens, B, T, pa, sd(3))

@@ -120,8 +120,8 @@ class InterCTCTapFn(torch.autograd.Function):
             be = enc.conditioning_layer._b
             dxc = ops.cast(dxo, cd)
             with ops.wgrad(dxc, p):
-                ops.colsum(dxc, be.g("bias"))
-                ops.linear_dw(dxc, p, be.g("weight"), accumulate=True)
+                ops.linear_dw(dxc, p, be.g("weight"), accumulate=True,
+                              db=be.g("bias"))
             dp = empty(N, V, dtype=cd, device=dev)
             ops.linear_dx(dxc, be.w("weight"), dp)
         if lat is None and dp is None:  # neither a loss nor conditioning: the tap only observed
@@ -140,8 +140,8 @@ class InterCTCTapFn(torch.autograd.Function):
             lib.ea_interctc_dlogits(B, T, V, logits.data_ptr(), V, None, None, 0, None, 0, lse.data_ptr(), None, None,
                                     None, None, 0.0, dp.data_ptr(), V, dl.data_ptr(), ops.dt(dl), V, ops.stream())
         with ops.wgrad(dl, h):
-            ops.colsum(dl, bc.g("ctc_lo.bias"))
-            ops.linear_dw(dl, h, bc.g("ctc_lo.weight"), accumulate=True)
+            ops.linear_dw(dl, h, bc.g("ctc_lo.weight"), accumulate=True,
+                          db=bc.g("ctc_lo.bias"))
         dy = empty(N, d, device=dev)
         ops.linear_dx(dl, bc.w("ctc_lo.weight"), dy)
         dx = dxo.clone()  # (dx' itself belongs to autograd)

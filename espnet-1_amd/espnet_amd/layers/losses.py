@@ -135,8 +135,8 @@ class CTCFn(torch.autograd.Function):
                                 nll.data_ptr(), gl.data_ptr(), 1.0 / B, dl.data_ptr(), ops.dt(dl), V,
                                 ops.stream())
             with ops.wgrad(dl, h):
-                ops.colsum(dl, b.g("ctc_lo.bias"))
-                ops.linear_dw(dl, h, b.g("ctc_lo.weight"), accumulate=True)
+                ops.linear_dw(dl, h, b.g("ctc_lo.weight"), accumulate=True,
+                              db=b.g("ctc_lo.bias"))
             ops.linear_dx(dl, b.w("ctc_lo.weight"), dh)
             if ctc.dropout_rate > 0:
                 ops.scale_dropout(dh, dh, p=ctc.dropout_rate, seed=ctc._seed)

@@ -121,8 +121,8 @@ class TransformerBlockFn(torch.autograd.Function):
         ops.linear_dx(dv, b.w("feed_forward.w_2.weight"), dh,
                       epi=ops.make_epi(EPI_DACT, act=ACT_RELU, aux=h, drop_p=p_ff, seed=sd(3)))
         with ops.wgrad(dh, xn2):
-            ops.colsum(dh, b.g("feed_forward.w_1.bias"))
-            ops.linear_dw(dh, xn2, b.g("feed_forward.w_1.weight"), accumulate=True)
+            ops.linear_dw(dh, xn2, b.g("feed_forward.w_1.weight"), accumulate=True,
+                          db=b.g("feed_forward.w_1.bias"))
         dxn = empty(N, d, dtype=cd, device=dev)
         ops.linear_dx(dh, b.w("feed_forward.w_1.weight"), dxn)
         ln_bwd(dxn, x1, b, "norm2", mu2, rs2, dx, accumulate=True)
@@ -138,8 +138,8 @@ class TransformerBlockFn(torch.autograd.Function):
                  ldv=3 * d, klen=olens, causal=getattr(L, "causal", False), scale=scale, p=pa, seed=sd(1), cd=cd, dq=dqkv, lddq=3 * d,
                  dk_=dqkv[:, d:], lddk=3 * d, dv=dqkv[:, 2 * d:], lddv=3 * d)
         with ops.wgrad(dqkv, xn1):
-            ops.colsum(dqkv, b.g(*_QKV_B, shape=(3 * d,)))
-            ops.linear_dw(dqkv, xn1, b.g(*_QKV_W, shape=(3 * d, d)), accumulate=True)
+            ops.linear_dw(dqkv, xn1, b.g(*_QKV_W, shape=(3 * d, d)), accumulate=True,
+                          db=b.g(*_QKV_B, shape=(3 * d,)))
         dxn = empty(N, d, dtype=cd, device=dev)
         ops.linear_dx(dqkv, b.w(*_QKV_W, shape=(3 * d, d)), dxn)
         ln_bwd(dxn, x0, b, "norm1", mu1, rs1, dx, accumulate=True)

@@ -165,7 +165,12 @@ int ea_gemm_ln(int M, int N, int K, const float* x, long ldx, const float* gamma
 
 /* One problem of a grouped launch: C[M,N] (f32, row stride ldc) = beta*C + op(A) op(B), bf16
  * operands in the layouts of ea_gemm (a_kmajor/b_kmajor shared by the group), lda/ldb
- * multiples of 8 elements, 16-B aligned bases, N and ldc multiples of 4. */
+ * multiples of 8 elements, 16-B aligned bases, N and ldc multiples of 4.
+ * a_sum (NULL: none): a_sum[m] = beta*a_sum[m] + sum_k op(A)[m,k] for m < M, f32, 4-B aligned
+ * — the Linear bias gradient (column sums of dY) from the operand the weight-gradient GEMM
+ * streams anyway.  Summed over the whole K inside the problem's first tile of each tile row, in
+ * the slice order of C, so the result does not depend on the other problems of the call.  It
+ * must not overlap any C or any other a_sum of the call. */
 typedef struct ea_group_gemm {
   const void* A;
   const void* B;
@@ -173,6 +178,7 @@ typedef struct ea_group_gemm {
   long lda, ldb, ldc;
   int M, N, K;
   float beta;
+  float* a_sum;
 } ea_group_gemm;
 /* n independent GEMMs in ONE launch, every tile 256x256 over the problem's whole K on the
  * pipelined main loop (problems in the given order: put the longest K first).  Replaces the
