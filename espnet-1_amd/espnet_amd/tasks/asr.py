@@ -21,6 +21,7 @@ import numpy as np
 
 from ..asr.abs_modules import AbsFrontend, AbsNormalize, AbsSpecAug
 from ..asr.ctc import CTC
+from ..asr.decoder.rnn_decoder import RNNDecoder
 from ..asr.decoder.transformer_decoder import AbsDecoder, TransformerDecoder
 from ..asr.encoder.conformer_encoder import AbsEncoder, ConformerEncoder
 from ..asr.encoder.e_branchformer_encoder import EBranchformerEncoder
@@ -43,8 +44,8 @@ model_choices = ClassChoices("model", dict(espnet=ESPnetASRModel), type_check=Ab
 encoder_choices = ClassChoices("encoder", dict(conformer=ConformerEncoder, transformer=TransformerEncoder,
                                                e_branchformer=EBranchformerEncoder),
                                type_check=AbsEncoder, default="rnn")
-decoder_choices = ClassChoices("decoder", dict(transformer=TransformerDecoder), type_check=AbsDecoder, default=None,
-                               optional=True)
+decoder_choices = ClassChoices("decoder", dict(transformer=TransformerDecoder, rnn=RNNDecoder), type_check=AbsDecoder,
+                               default=None, optional=True)
 # the registries the reference also exposes, empty here (nothing on the training path uses them)
 preencoder_choices = ClassChoices("preencoder", dict(), default=None, optional=True)
 postencoder_choices = ClassChoices("postencoder", dict(), default=None, optional=True)

@@ -191,7 +191,7 @@ class CapturedTrainStep:
         if not getattr(m.encoder, "interctc_layer_idx", None):
             # (an encoder with intermediate-CTC taps loops over its layers itself and draws nothing)
             layerdrop_draw(len(m.encoder.encoders))
-        if m.decoder is not None:
+        if getattr(m.decoder, "decoders", None) is not None:  # (the RNN decoder has no MultiSequential)
             layerdrop_draw(len(m.decoder.decoders))
 
     # ------------------------------------------------------------------ step

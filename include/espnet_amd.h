@@ -924,6 +924,50 @@ int ea_lstm_cell_bwd(int wdtype, int n, int H, const void* wpack_t, const void* 
                      const float* c_prev, long ldc, const float* dc_in, float* dc_out, long lddc,
                      float* dgates, void* dgates_b, long ldd, float* dh_tot, long ldt, void* stream);
 
+/* ---------------------------------------------------------------- RNNDecoder (location attention) */
+
+/* One step of the location-aware attention AttLoc (espnet/nets/pytorch_backend/rnn/attentions.py:
+ * 249-379) for B utterances, and its backward.  With F = aconv_filts, C = aconv_chans, A = adim,
+ * E the encoder width, n = hlens[b] clamped to [0, T]:
+ *   conv[t,c] = sum_k conv_w[c,k] aprev[b, t+k-F]                    (aprev = 0 outside [0, n))
+ *   e[t]      = gvec_b + sum_a gvec_w[a] tanh(pre_enc[b,t,a] + dec[b,a] + sum_c att_w[a,c] conv[t,c])
+ *   w[b,t]    = softmax_t(2 e[t]) over t < n, exactly 0 for n <= t < T
+ *   c[b,:]    = sum_t w[b,t] hs[b,t,:]
+ * aprev NULL is the first step: aprev[b,t] = 1 / n for t < n.  Frames t >= n of hs, pre_enc and
+ * aprev are never read.  mdtype (EA_F32 / EA_BF16) is the element type of hs and pre_enc; every
+ * other tensor, every sum, tanhf, expf and the softmax are f32.  Any T, A, C, E >= 1, F >= 0.
+ *  hs (B, T, E): row stride ldhs, utterance stride shs; pre_enc (B, T, A): ldpre, spre (elements).
+ *  hlens: B int64.  dec (B, A), aprev (B, T), w (B, T), c (B, E): f32 with their row strides.
+ *  conv_w (C, 2F+1), att_w (A, C), gvec_w (A), gvec_b (1): f32, dense.
+ *  ws: f32 scratch; ea_attloc_fwd needs B*T*(1 + C) floats, ea_attloc_bwd
+ *    B*T*(1 + (3 + ceil(A/64))*C) floats.
+ *
+ * ea_attloc_bwd takes the step's dec, aprev, the w the forward wrote, dc (B, E) and the gradient
+ * dw_next (B, T) that the NEXT step's launch left in its daprev (NULL at the last step), recomputes
+ * conv and u = tanh(..) and writes, with dw[t] = hs[b,t,:] . dc[b,:] + dw_next[b,t],
+ * de[t] = 2 w[t] (dw[t] - sum_u w[u] dw[u]), dp[t,a] = de[t] gvec_w[a] (1 - u[t,a]^2):
+ *   dpre[b,t,a] += dp[t,a]                       dhs[b,t,:] += w[b,t] dc[b,:]      (t < n)
+ *   ddec[b,a]    = sum_t dp[t,a]
+ *   daprev[b,s]  = sum_{t,c} dconv[t,c] conv_w[c, s-t+F],  dconv[t,c] = sum_a dp[t,a] att_w[a,c]
+ *                  (0 for s >= n; daprev NULL: not computed, the first step needs none)
+ *   part[b,:]   += this utterance's terms of [d att_w (A*C) | d conv_w (C*(2F+1)) | d gvec_w (A) |
+ *                  d gvec_b (1)]; ldpart >= A*C + C*(2F+1) + A + 1.  The caller zeroes part before
+ *                  the first step and sums its rows (ea_colsum) after the last.
+ * No atomics: every output element has one owning thread and every sum a fixed order, so equal
+ * inputs give bit-equal outputs.  daprev must not alias dw_next, w or aprev. */
+int ea_attloc_fwd(int mdtype, int B, int T, int E, int A, int C, int F, const void* hs, long ldhs,
+                  long shs, const void* pre_enc, long ldpre, long spre, const long long* hlens,
+                  const float* dec, long lddec, const float* aprev, long ldap, const float* conv_w,
+                  const float* att_w, const float* gvec_w, const float* gvec_b, float* w, long ldw,
+                  float* c, long ldc, float* ws, long ws_floats, void* stream);
+int ea_attloc_bwd(int mdtype, int B, int T, int E, int A, int C, int F, const void* hs, long ldhs,
+                  long shs, const void* pre_enc, long ldpre, long spre, const long long* hlens,
+                  const float* dec, long lddec, const float* aprev, long ldap, const float* w, long ldw,
+                  const float* conv_w, const float* att_w, const float* gvec_w, const float* dc,
+                  long lddc, const float* dw_next, long lddwn, float* dpre, long lddpre, long sdpre,
+                  float* dhs, long lddhs, long sdhs, float* ddec, long ldddec, float* daprev, long ldda,
+                  float* part, long ldpart, float* ws, long ws_floats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
