@@ -14,14 +14,18 @@ Training forward (time-major rows i * B + b, f32 between the nodes, bf16 matrix 
                                 hidden state): mlp_enc and the embedding half of layer 0's input
                                 projection are ONE GEMM each over all rows; per step mlp_dec of the
                                 query, ea_attloc_fwd, the context half of the projection and
-                                ea_lstm_cell_fwd; the backward walks the steps in reverse
-                                (ea_lstm_cell_bwd, ea_attloc_bwd) and takes every weight gradient
-                                from GEMMs / column sums over all steps after the loop
-    LSTMLayerFn x (layers - 1)  lm/rnn_train.py's node, zero initial state (+ DropFn between)
+                                the cell step; the backward walks the steps in reverse (the cell
+                                step, ea_attloc_bwd) and takes every weight gradient from GEMMs /
+                                column sums over all steps after the loop.  The state buffers, both
+                                cell steps and layer 0's weight gradients are lm/rnn_train.py's
+                                LSTMTape, as in LSTMLayerFn
+    LSTMLayerFn x (layers - 1)  zero initial state (+ DropFn between)
     DropFn, OutLinearFn         logits; OutMaskFn zeroes the rows past ys_in_lens
 
-Lengths stay on the device; forward and backward make no host synchronisation.  The LSTM kernels
-read HHPacks of weight_hh, rebuilt after every optimizer step (ParamArena.update_hooks).
+The nodes take the handles bind() builds (lm/rnn_train.py): an LSTMLayer per cell, whose HHPacks of
+weight_hh are rebuilt after every optimizer step (ParamArena.update_hooks), the EmbedTable of embed
+and the LinearHead of output.  Lengths stay on the device; forward and backward make no host
+synchronisation.
 
 Decoding: init_state / score / batch_score with the reference's state dict (c_prev, z_prev, a_prev,
 workspace).  batch_score runs the running hypotheses as the rows of ONE step (one ea_attloc_fwd,
@@ -30,16 +34,16 @@ utterance (the reference's reset() / pre_compute_enc_h protocol).
 """
 from __future__ import annotations
 
-import types
 from typing import Any, List, Tuple
 
 import torch
 
 from ... import hip_ops as ops
-from ..._lib import BF16, EPI_RESID, F32, lib
+from ..._lib import EPI_RESID, lib
 from ...layers.common import Bound, site_seed
-from ...lm.lstm_pack import HHPacks, rup
-from ...lm.rnn_train import DropFn, EmbedFn, LSTMLayerFn, OutLinearFn, _f32c
+from ...lm.lstm_pack import rup
+from ...lm.rnn_train import (DropFn, EmbedFn, EmbedTable, LinearHead, LSTMLayer, LSTMLayerFn, LSTMTape, OutLinearFn,
+                               f32c)
 from .transformer_decoder import AbsDecoder
 
 _ATT_DEFAULTS = dict(atype="location", num_att=1, num_encs=1, aheads=4, adim=320, awin=5, aconv_chans=10,
@@ -103,33 +107,21 @@ class AttLocLSTM0Fn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, eys, hs_pad, dec, hlens, L, B, p, query_seeds):
-        b, att = dec._b, dec.att_list[0]
-        cd = b.cd
-        bf = cd == torch.bfloat16
-        wd = BF16 if bf else F32
-        H, dev = dec.dunits, eys.device
+        b, att, lay = dec._b, dec.att_list[0], dec._layers[0]
+        cd, bf, wd, w_ih = lay.cd, lay.bf, lay.wd, lay.w_ih
+        H, dev = lay.H, eys.device
         T, E, A = hs_pad.shape[1], att.eprojs, att.att_dim
-        Hp, G, I = rup(H), 4 * H, H + E
-        st = ops.stream()
-        w_ih, w_dec = b.w("decoder.0.weight_ih"), b.w("att_list.0.mlp_dec.weight")
-        bsum = dec.decoder[0].bias_ih.detach() + dec.decoder[0].bias_hh.detach()
+        w_dec = b.w("att_list.0.mlp_dec.weight")
+        bsum = lay.bias_sum()
         hs_c = ops.cast(hs_pad.reshape(B * T, E), cd)
         pre = torch.empty(B * T, A, dtype=cd, device=dev)
         ops.linear(hs_c, b.w("att_list.0.mlp_enc.weight"), pre, epi=ops.make_epi(bias=b.f("att_list.0.mlp_enc.bias")))
         # layer 0's input rows [eys | c]: the embedding half now, the context half step by step
-        x0 = torch.empty(L * B, I, dtype=cd, device=dev)
+        x0 = torch.empty(L * B, lay.I, dtype=cd, device=dev)
         ops.scale_dropout(eys, x0[:, :H])
-        xproj = torch.empty(L * B, G, device=dev)
-        ops.linear(x0[:, :H], w_ih[:, :H], xproj, epi=ops.make_epi(bias=bsum))
-        zs = torch.empty(L + 1, B, Hp, device=dev)
-        cs = torch.empty(L + 1, B, Hp, device=dev)
-        zb = torch.empty(L + 1, B, Hp, dtype=torch.bfloat16, device=dev) if bf else None
-        gates = torch.empty(L, B, G, device=dev)
-        zs[0].zero_()
-        cs[0].zero_()
-        if bf:
-            zb[0].zero_()
-        zin = zb if bf else zs
+        xproj = lay.input_proj(x0[:, :H], w_ih[:, :H], bsum)
+        tape = LSTMTape(lay, L, B, dev)
+        zs, zin = tape.hs, tape.hin
         # the queries dropout(z0_{i-1}) in the compute dtype: the states themselves when p = 0
         qs = torch.empty(L, B, H, dtype=cd, device=dev) if p > 0.0 else zin[:L, :, :H]
         if p > 0.0:
@@ -138,7 +130,7 @@ class AttLocLSTM0Fn(torch.autograd.Function):
         q[0].zero_()  # the first query is the zero state
         w = torch.empty(L, B, T, device=dev)
         cf = None if not bf else torch.empty(B, E, device=dev)
-        pack = dec._hh[0].fwd.data_ptr()
+        cell = tape.fwd_steps(xproj)
         for i in range(L):
             rows = slice(i * B, (i + 1) * B)
             if i > 0:
@@ -150,32 +142,24 @@ class AttLocLSTM0Fn(torch.autograd.Function):
             if bf:
                 ops.scale_dropout(cf, x0[rows, H:])
             ops.linear(x0[rows, H:], w_ih[:, H:], xproj[rows], epi=ops.make_epi(beta=1.0))
-            lib.ea_lstm_cell_fwd(wd, B, H, pack, xproj[rows].data_ptr(), G, zin[i].data_ptr(), cs[i].data_ptr(), Hp,
-                                 zs[i + 1].data_ptr(), cs[i + 1].data_ptr(), Hp, zb[i + 1].data_ptr() if bf else None,
-                                 gates[i].data_ptr(), G, st)
-        ctx.save = (dec, hlens, L, B, T, p, query_seeds, hs_c, pre, x0, zs, cs, zb, gates, qs, q, w)
+            cell(i)
+        ctx.save = (dec, hlens, T, p, query_seeds, hs_c, pre, x0, tape, qs, q, w)
         dec._last_att_w = w.detach()
-        return zs[1:].view(L * B, Hp)[:, :H]
+        return tape.outputs()
 
     @staticmethod
     def backward(ctx, dy):
-        dec, hlens, L, B, T, p, query_seeds, hs_c, pre, x0, zs, cs, zb, gates, qs, q, w = ctx.save
+        dec, hlens, T, p, query_seeds, hs_c, pre, x0, tape, qs, q, w = ctx.save
         ctx.save = None
-        b, att = dec._b, dec.att_list[0]
-        cd = b.cd
-        bf = cd == torch.bfloat16
-        wd = BF16 if bf else F32
-        H, dev = dec.dunits, dy.device
+        b, att, lay = dec._b, dec.att_list[0], tape.layer
+        cd, wd, w_ih, L, B = lay.cd, lay.wd, lay.w_ih, tape.T, tape.B
+        H, G, dev = lay.H, lay.G, dy.device
         E, A, C, F = att.eprojs, att.att_dim, att.aconv_chans, att.aconv_filts
-        Hp, G = rup(H), 4 * H
-        ldd = rup(G)
         st = ops.stream()
-        w_ih, w_dec = b.w("decoder.0.weight_ih"), b.w("att_list.0.mlp_dec.weight")
-        dz = _f32c(dy).contiguous().clone()  # (L*B, H): step i's rows also collect the next query's gradient
-        dg = torch.empty(L, B, ldd, device=dev)
-        dgb = torch.empty(L, B, ldd, dtype=torch.bfloat16, device=dev) if bf else None
-        dgn = dgb if bf else dg
-        dcell = torch.empty(2, B, Hp, device=dev)
+        w_dec = b.w("att_list.0.mlp_dec.weight")
+        dz = f32c(dy).contiguous().clone()  # (L*B, H): step i's rows also collect the next query's gradient
+        cell = tape.bwd_steps(dz, H)
+        dgn = tape.dgn
         dctx = torch.empty(B, E, device=dev)
         dwc = torch.empty(2, B, T, device=dev)  # the attention-weight gradient carried to the step before
         dq = torch.empty(L, B, A, device=dev)
@@ -184,15 +168,10 @@ class AttLocLSTM0Fn(torch.autograd.Function):
         nK = C * (2 * F + 1)
         part = torch.zeros(B, A * C + nK + A + 1, device=dev)
         ws = _attloc_ws(B, T, A, C, dev, bwd=True)
-        pack_t = dec._hh[0].bwd.data_ptr()
         kw, mw, gw = (b.f(f"att_list.0.{n}.weight").data_ptr() for n in ("loc_conv", "mlp_att", "gvec"))
         for i in range(L - 1, -1, -1):
             last = i == L - 1
-            rows = slice(i * B, (i + 1) * B)
-            lib.ea_lstm_cell_bwd(wd, B, H, pack_t, None if last else dgn[i + 1].data_ptr(), ldd, dz[rows].data_ptr(), H,
-                                 gates[i].data_ptr(), G, cs[i + 1].data_ptr(), cs[i].data_ptr(), Hp,
-                                 None if last else dcell[(i + 1) & 1].data_ptr(), dcell[i & 1].data_ptr(), Hp,
-                                 dg[i].data_ptr(), dgb[i].data_ptr() if bf else None, ldd, None, 0, st)
+            cell(i)
             ops.linear_dx(dgn[i][:, :G], w_ih[:, H:], dctx)
             lib.ea_attloc_bwd(wd, B, T, E, A, C, F, hs_c.data_ptr(), E, T * E, pre.data_ptr(), A, T * A,
                               hlens.data_ptr(), q[i].data_ptr(), A, w[i - 1].data_ptr() if i else None, T,
@@ -203,18 +182,12 @@ class AttLocLSTM0Fn(torch.autograd.Function):
             if i > 0:  # dz0_{i-1} += dropout-mask(dq_i . W_dec)
                 ops.linear_dx(ops.cast(dq[i], cd), w_dec, dz[(i - 1) * B:i * B],
                               epi=ops.make_epi(EPI_RESID, resid=dz[(i - 1) * B:i * B], drop_p=p, seed=query_seeds[i]))
-        dgm = dgn.view(L * B, ldd)[:, :G]
+        dgm = tape.dgm
         deys = None
         if ctx.needs_input_grad[0]:
             deys = torch.empty(L * B, H, device=dev)
             ops.linear_dx(dgm, w_ih[:, :H], deys)
-        cell = dec.decoder[0]
-        zprev = (zb if bf else zs)[:L].view(L * B, Hp)[:, :H]
-        ops.linear_dw(dgm, x0, cell.weight_ih.grad, accumulate=True)
-        ops.linear_dw(dgm, zprev, cell.weight_hh.grad, accumulate=True)
-        dg32 = dg.view(L * B, ldd)[:, :G]
-        ops.colsum(dg32, cell.bias_ih.grad, accumulate=True)
-        ops.colsum(dg32, cell.bias_hh.grad, accumulate=True)
+        zprev = tape.weight_grads(x0)
         ops.linear_dw(ops.cast(dq.view(L * B, A), cd), qs.reshape(L * B, H) if p > 0.0 else zprev,
                       att.mlp_dec.weight.grad, accumulate=True)
         dpre_c = ops.cast(dpre, cd)
@@ -245,36 +218,6 @@ class OutMaskFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         return dy.masked_fill(~ctx.keep, 0.0), None
-
-
-class _LMView:
-    """The attributes lm/rnn_train.py's nodes read from a SequentialRNNLM, mapped onto this decoder:
-    encoder = embed, rnn.*_l{k} = decoder[k].*, decoder = output."""
-
-    def __init__(self, dec):
-        self._dec = dec
-        self.encoder, self.decoder = dec.embed, dec.output
-        self.ninp = self.nhid = dec.dunits
-        self.vocab_size = dec.odim
-        self.rnn = types.SimpleNamespace()
-        for k, cell in enumerate(dec.decoder):
-            for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh"):
-                setattr(self.rnn, f"{n}_l{k}", getattr(cell, n))
-        self._pe0 = torch.zeros(1, self.ninp, device=dec._b.arena.device)
-
-    @property
-    def _cd(self):
-        return self._dec._b.cd
-
-    @property
-    def _hh(self):
-        return self._dec._hh
-
-    def _w(self, name: str) -> torch.Tensor:
-        if name == "decoder.weight":
-            return self._dec._b.w("output.weight")
-        leaf, k = name[len("rnn."):].rsplit("_l", 1)
-        return self._dec._b.w(f"decoder.{k}.{leaf}")
 
 
 class RNNDecoder(AbsDecoder):
@@ -341,9 +284,10 @@ class RNNDecoder(AbsDecoder):
         return []  # no fused weights: every GEMM reads one parameter (or a column slice of one)
 
     def bind(self, arena, prefix, cd):
-        self._b = Bound(arena, prefix, cd)
-        self._lm = _LMView(self)
-        self._hh = [HHPacks(cell.weight_hh, cd) for cell in self.decoder]
+        self._b = b = Bound(arena, prefix, cd)
+        self._embed = EmbedTable(self.embed, arena.device)
+        self._layers = [LSTMLayer(cell, b.w(f"decoder.{k}.weight_ih"), cd) for k, cell in enumerate(self.decoder)]
+        self._head = LinearHead(self.output, b.w("output.weight"), cd)
         self._mem = None
         self._last_att_w = None
         self._anchor = torch.zeros(1, device=arena.device, requires_grad=True)
@@ -351,8 +295,8 @@ class RNNDecoder(AbsDecoder):
         self._weights_changed()
 
     def _weights_changed(self):
-        for hh, cell in zip(self._hh, self.decoder):
-            hh.refresh(cell.weight_hh)
+        for lay in self._layers:
+            lay.refresh()
         self._mem = None  # a cached mlp_enc projection belongs to the old weights
 
     # ------------------------------------------------------------------ training
@@ -369,8 +313,7 @@ class RNNDecoder(AbsDecoder):
                 ys_in_lens: torch.Tensor, seed: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
         if self._b is None:
             raise RuntimeError("RNNDecoder: bind(arena, prefix, cd) first (ESPnetASRModel.prepare)")
-        lm, V = self._lm, self.odim
-        dev = hs_pad.device
+        V, dev = self.odim, hs_pad.device
         B, L = ys_in_pad.shape
         if B == 0 or L == 0 or hs_pad.shape[1] == 0:
             raise ValueError(f"empty batch: {tuple(ys_in_pad.shape)}, {tuple(hs_pad.shape)}")
@@ -379,17 +322,17 @@ class RNNDecoder(AbsDecoder):
         tok = ys_in_pad.to(dev, torch.long).t().clamp(0, V - 1).contiguous().view(-1)  # row i * B + b
         p = float(self.dropout) if self.training else 0.0
         seeds = self.dropout_seeds(seed, L)
-        x = EmbedFn.apply(self._anchor, tok, lm)
+        x = EmbedFn.apply(self._anchor, tok, self._embed)
         if p > 0.0:
             x = DropFn.apply(x, p, seeds["emb"])
         x = AttLocLSTM0Fn.apply(x, hs_pad.contiguous().float(), self, hlens, L, B, p, seeds["query"])
         for l in range(1, self.dlayers):
             if p > 0.0:
                 x = DropFn.apply(x, p, seeds[f"layer{l}"])
-            x, _, _ = LSTMLayerFn.apply(x, lm, l, L, B, None, None)
+            x, _, _ = LSTMLayerFn.apply(x, self._layers[l], L, B, None, None)
         if p > 0.0:
             x = DropFn.apply(x, p, seeds["out"])
-        y = OutLinearFn.apply(x, lm)
+        y = OutLinearFn.apply(x, self._head)
         return OutMaskFn.apply(y.view(L, B, V).transpose(0, 1), ys_in_lens), ys_in_lens
 
     # ------------------------------------------------------------------ decoding
@@ -431,9 +374,7 @@ class RNNDecoder(AbsDecoder):
         if self._b is None:
             raise RuntimeError("RNNDecoder: bind(arena, prefix, cd) first (ESPnetASRModel.prepare)")
         b, att = self._b, self.att_list[0]
-        cd = b.cd
-        bf = cd == torch.bfloat16
-        wd = BF16 if bf else F32
+        cd, bf, wd = b.cd, self._layers[0].bf, self._layers[0].wd
         n = ys.shape[0]
         if len(states) != n or xs.shape[0] != n:
             raise ValueError(f"{len(states)} states, {xs.shape[0]} memories for {n} prefixes")
@@ -458,7 +399,7 @@ class RNNDecoder(AbsDecoder):
                                else s["a_prev"].reshape(1, T).to(dev, torch.float32) for s in states])
         tok = ys[:, -1].to(dev, torch.long).clamp(0, V - 1).contiguous()
         ey = torch.empty(n, H, device=dev)
-        lib.ea_embed_fwd(n, H, 1, tok.data_ptr(), b.f("embed.weight").data_ptr(), 1.0, self._lm._pe0.data_ptr(), 0.0, 0,
+        lib.ea_embed_fwd(n, H, 1, tok.data_ptr(), b.f("embed.weight").data_ptr(), 1.0, self._embed.pe0.data_ptr(), 0.0, 0,
                          ey.data_ptr(), st)
         x0 = torch.empty(n, H + E, dtype=cd, device=dev)
         ops.scale_dropout(ey, x0[:, :H])
@@ -475,11 +416,12 @@ class RNNDecoder(AbsDecoder):
         zb = torch.empty(NL, n, Hp, dtype=torch.bfloat16, device=dev) if bf else None
         gates = torch.empty(n, G, device=dev)
         xin = x0
-        for l, cell in enumerate(self.decoder):
+        # the layers are this step's rows: each has its own pack and reads the cast copy zpc of the
+        # previous states, so LSTMTape's step (one pack, hs[t] -> hs[t + 1]) does not fit these buffers
+        for l, lay in enumerate(self._layers):
             xproj = torch.empty(n, G, device=dev)
-            ops.linear(xin, b.w(f"decoder.{l}.weight_ih"), xproj,
-                       epi=ops.make_epi(bias=cell.bias_ih.detach() + cell.bias_hh.detach()))
-            lib.ea_lstm_cell_fwd(wd, n, H, self._hh[l].fwd.data_ptr(), xproj.data_ptr(), G, zpc[l].data_ptr(),
+            ops.linear(xin, lay.w_ih, xproj, epi=ops.make_epi(bias=lay.bias_sum()))
+            lib.ea_lstm_cell_fwd(wd, n, H, lay.hh.fwd.data_ptr(), xproj.data_ptr(), G, zpc[l].data_ptr(),
                                  cp[l].data_ptr(), Hp, zn[l].data_ptr(), cn[l].data_ptr(), Hp,
                                  zb[l].data_ptr() if bf else None, gates.data_ptr(), G, st)
             xin = (zb if bf else zn)[l, :, :H]

@@ -15,8 +15,9 @@ with their rows zero padded to a multiple of EA_LSTM_KG.  A step's states live i
 (2, nlayers, n, Hp) buffer; batch_score returns views of it and recognises them when they come
 back, so the beam's reordering costs an index vector and no copy.
 
-prepare(train=True) adds the training path (rnn_train.py): in training mode with autograd,
-forward runs the embedding, the dropouts, one autograd node per LSTM layer (one GEMM for the
+prepare(train=True) adds the training path (rnn_train.py's nodes, on the handles _bind_train
+builds: an LSTMLayer per layer, the embedding table, the output head): in training mode with
+autograd, forward runs the embedding, the dropouts, one autograd node per LSTM layer (one GEMM for the
 input projection of all time steps, then ea_lstm_cell_fwd / ea_lstm_cell_bwd once per step) and
 the output Linear over the whole padded batch.  The recurrent kernels' packs of weight_hh are
 rebuilt on the device after every optimizer step (ParamArena.update_hooks) and the scorer's
@@ -35,9 +36,9 @@ from torch import nn
 from .. import hip_ops as ops
 from .._lib import BF16, F32, lib
 from ..arena import ParamArena
-from ..layers.common import site_seed
+from ..layers.common import Bound, site_seed
 from .lstm_pack import HHPacks, pack_lstm_bias, pack_lstm_hh, pack_lstm_hh_t, pack_lstm_weights, rup
-from .rnn_train import DropFn, EmbedFn, LSTMLayerFn, OutLinearFn
+from .rnn_train import DropFn, EmbedFn, EmbedTable, LinearHead, LSTMLayer, LSTMLayerFn, OutLinearFn
 
 # the pack functions stay importable from this module, where callers found them before lstm_pack.py
 __all__ = ["SequentialRNNLM", "HHPacks", "pack_lstm_bias", "pack_lstm_hh", "pack_lstm_hh_t", "pack_lstm_weights"]
@@ -100,10 +101,7 @@ class SequentialRNNLM(nn.Module):
         self._prefix = "" if owner is None else "lm."
         self.arena = ParamArena(self if owner is None else owner, device, shadow_dtype=self._cd if train else None)
         if train:
-            self._anchor = torch.zeros(1, device=device, requires_grad=True)
-            self._pe0 = torch.zeros(1, self.ninp, device=device)  # ea_embed_fwd adds a position row
-            self._hh = [HHPacks(getattr(self.rnn, f"weight_hh_l{k}"), self._cd) for k in range(self.nlayers)]
-            self.arena.update_hooks.append(self._weights_changed)
+            self._bind_train(Bound(self.arena, self._prefix, self._cd))
         self._recent = {}  # storage pointer -> (state buffer, states handed out) of the last two steps
         self._handed = {}  # id(state tuple) -> (the tuple, its buffer, its row)
         self.repack()
@@ -112,16 +110,21 @@ class SequentialRNNLM(nn.Module):
             self.__dict__["_hooked"] = True
         return self
 
+    def _bind_train(self, b: Bound):
+        """The training nodes' handles (rnn_train.py) over the arena views of b."""
+        dev = b.arena.device
+        self._anchor = torch.zeros(1, device=dev, requires_grad=True)
+        self._embed = EmbedTable(self.encoder, dev)
+        self._layers = [LSTMLayer(self.rnn, b.w(f"rnn.weight_ih_l{k}"), b.cd, k) for k in range(self.nlayers)]
+        self._head = LinearHead(self.decoder, b.w("decoder.weight"), b.cd)
+        b.arena.update_hooks.append(self._weights_changed)
+
     def _weights_changed(self):
         """After an optimizer step (or a shadow refresh): the recurrent packs now, on the
         stream, the scorer's packs at the next eval call."""
-        for k, hh in enumerate(self._hh):
-            hh.refresh(getattr(self.rnn, f"weight_hh_l{k}"))
+        for lay in self._layers:
+            lay.refresh()
         self._stale = True
-
-    def _w(self, name: str) -> torch.Tensor:
-        """A weight in the compute dtype: the arena's bf16 shadow under amp, else the master."""
-        return self.arena.view(self._prefix + name, which="shadow" if self._cd == torch.bfloat16 else "data")
 
     @torch.no_grad()
     def repack(self):
@@ -328,7 +331,7 @@ class SequentialRNNLM(nn.Module):
         seeds = self.dropout_seeds(self._nstep)
         self._nstep += 1
         p, p_rnn = float(self.drop.p), float(self.rnn.dropout)
-        x = EmbedFn.apply(self._anchor, tok, self)
+        x = EmbedFn.apply(self._anchor, tok, self._embed)
         if p > 0.0:
             x = DropFn.apply(x, p, seeds["embed"])
         hn, cn = [], []
@@ -337,14 +340,14 @@ class SequentialRNNLM(nn.Module):
             if hidden is not None:
                 h0 = hidden[0][k].detach().to(self._device, torch.float32)
                 c0 = hidden[1][k].detach().to(self._device, torch.float32)
-            x, h, c = LSTMLayerFn.apply(x, self, k, T, B, h0, c0)
+            x, h, c = LSTMLayerFn.apply(x, self._layers[k], T, B, h0, c0)
             hn.append(h)
             cn.append(c)
             if k < L - 1 and p_rnn > 0.0:
                 x = DropFn.apply(x, p_rnn, seeds[f"rnn{k}"])
         if p > 0.0:
             x = DropFn.apply(x, p, seeds["out"])
-        y = OutLinearFn.apply(x, self)
+        y = OutLinearFn.apply(x, self._head)
         return y.view(T, B, V).transpose(0, 1), (torch.stack(hn), torch.stack(cn))
 
     def _forward(self, input, hidden):

@@ -83,7 +83,8 @@ def recurrent_launch(model, amp):
     dg = torch.empty(T, B, ldd, device=dev)
     dgb = torch.empty(T, B, ldd, dtype=torch.bfloat16, device=dev)
     dc = torch.empty(2, B, Hp, device=dev)
-    pk, pkt = lm._hh[0].fwd.data_ptr(), lm._hh[0].bwd.data_ptr()
+    hh = lm._layers[0].hh
+    pk, pkt = hh.fwd.data_ptr(), hh.bwd.data_ptr()
     hin = hb if amp else hs
     dgn = dgb if amp else dg
 

@@ -87,6 +87,32 @@ def test_forward_before_binding_raises():
         _dec()(torch.zeros(1, 2, 16), torch.tensor([2]), torch.zeros(1, 1, dtype=torch.long), torch.tensor([1]))
 
 
+def test_layer_handles_hold_the_modules_parameters():
+    """The LSTMLayer handles of both recurrent models, built over a CPU arena: each holds the very
+    Parameters of its module (identity, so the kernels' gradients land in the arena's views), and
+    its I / H are the layer's (the decoder's layer 0 reads [eys | context])."""
+    from espnet_amd.arena import ParamArena
+    from espnet_amd.asr.decoder.rnn_decoder import RNNDecoder
+    from espnet_amd.layers.common import Bound
+    from espnet_amd.lm import SequentialRNNLM
+    names = ("weight_ih", "weight_hh", "bias_ih", "bias_hh")
+    lm = SequentialRNNLM(11, unit=5, nhid=3, nlayers=2)
+    lm._bind_train(Bound(ParamArena(lm, "cpu"), "", torch.float32))
+    dec = RNNDecoder(11, 6, num_layers=2, hidden_size=3)
+    dec.bind(ParamArena(dec, "cpu"), "", torch.float32)
+    assert len(lm._layers) == 2 and len(dec._layers) == 2
+    for k, (lay, dlay) in enumerate(zip(lm._layers, dec._layers)):
+        for n in names:
+            assert getattr(lay, n) is getattr(lm.rnn, f"{n}_l{k}"), (k, n)
+            assert getattr(dlay, n) is getattr(dec.decoder[k], n), (k, n)
+            assert getattr(lay, n).grad is not None and getattr(dlay, n).grad is not None
+        assert lay.w_ih.data_ptr() == lay.weight_ih.data_ptr() and dlay.w_ih.data_ptr() == dlay.weight_ih.data_ptr()
+    assert [(lay.I, lay.H) for lay in lm._layers] == [(5, 3), (3, 3)]
+    assert [(lay.I, lay.H) for lay in dec._layers] == [(9, 3), (3, 3)]
+    assert lm._embed.weight is lm.encoder.weight and lm._head.weight is lm.decoder.weight
+    assert dec._embed.weight is dec.embed.weight and dec._head.bias is dec.output.bias
+
+
 def test_task_builds_the_recipe_decoder():
     """ASRTask + `decoder: rnn` with the decoder_conf of egs2/aishell/asr1/conf/train_asr_rnn.yaml
     over the tiny_hybrid encoder: the reference's parameter count."""

@@ -295,10 +295,10 @@ def test_reference_checkpoint_round_trip():
     for k, v in ref_sd.items():
         assert torch.equal(back[k].cpu(), v), k
     for l, cell in enumerate(dec.decoder):
-        assert torch.equal(dec._hh[l].fwd, pack_lstm_hh(cell.weight_hh, torch.float32)), l
+        assert torch.equal(dec._layers[l].hh.fwd, pack_lstm_hh(cell.weight_hh, torch.float32)), l
     assert dec._mem is None
     dsd = {k[len("decoder."):]: v for k, v in ref_sd.items() if k.startswith("decoder.")}
     assert list(dsd) == list(dec.state_dict())
     dec.load_state_dict({k: v - 0.25 for k, v in dsd.items()})  # a submodule load refreshes too
     torch.cuda.synchronize()
-    assert torch.equal(dec._hh[0].fwd, pack_lstm_hh(dec.decoder[0].weight_hh, torch.float32))
+    assert torch.equal(dec._layers[0].hh.fwd, pack_lstm_hh(dec.decoder[0].weight_hh, torch.float32))

@@ -236,7 +236,7 @@ def test_embedding_backward_beyond_one_call():
     tok = torch.randint(0, V, (rows,), generator=gen)
     dx = torch.randn(rows, d, generator=gen)
     lm.arena.zero_grad()
-    x = EmbedFn.apply(lm._anchor, tok.cuda(), lm)
+    x = EmbedFn.apply(lm._anchor, tok.cuda(), lm._embed)
     assert torch.equal(x.cpu(), lm.encoder.weight.detach().cpu()[tok])
     x.backward(dx.cuda())
     got = lm.encoder.weight.grad.detach().cpu()
