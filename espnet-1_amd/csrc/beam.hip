@@ -21,7 +21,19 @@
 // Ties in a top-k break toward the lower index.
 #include "common.h"
 
+// One rounding per operation: device code is built with -ffp-contract=fast, under which
+// w_dec*logp + w_lb and W + w_ctc*ctc each became one fused multiply-add (the __fmul_rn /
+// __fadd_rn intrinsics are a plain * and + compiled in their header, where no pragma of this
+// file reaches) — an ulp off the reference's two roundings in the scores handed back, and two
+// scores the reference rounds to a tie could come out ordered.  The score arithmetic below
+// goes through mul_rn / add_rn / sub_rn, defined here under contract(off).
+#pragma clang fp contract(off)
+
 namespace {
+
+EA_DEV float mul_rn(float a, float b) { return a * b; }
+EA_DEV float add_rn(float a, float b) { return a + b; }
+EA_DEV float sub_rn(float a, float b) { return a - b; }
 
 struct Best {
   float v;
@@ -85,8 +97,8 @@ __global__ __launch_bounds__(PB_NT) void prebeam_kernel(int V, const float* __re
     const int v = v0 + e * 64 + lane;
     float wvv = -INFINITY;
     if (v < v1) {
-      wvv = __fmul_rn(w_dec, row[v]);
-      if (use_lb) wvv = __fadd_rn(wvv, w_lb);
+      wvv = mul_rn(w_dec, row[v]);
+      if (use_lb) wvv = add_rn(wvv, w_lb);
     }
     val[e] = wvv;
   }
@@ -184,10 +196,10 @@ __global__ __launch_bounds__(SEL_NT) void select_kernel(int n, int V, int P, int
       for (int q = 0; q < P; ++q) dup |= cand[h * (P + 1) + q] == j;
     const float lp = logp[(long)h * ld + j];
     const float ps = psi[c];
-    float wv = __fmul_rn(w_dec, lp);
-    if (use_lb) wv = __fadd_rn(wv, w_lb);
-    const float inc = __fsub_rn(ps, prefix[h]);
-    wv = __fadd_rn(__fadd_rn(wv, __fmul_rn(w_ctc, inc)), score[h]);
+    float wv = mul_rn(w_dec, lp);
+    if (use_lb) wv = add_rn(wv, w_lb);
+    const float inc = sub_rn(ps, prefix[h]);
+    wv = add_rn(add_rn(wv, mul_rn(w_ctc, inc)), score[h]);
     wsc[c] = dup ? -INFINITY : wv;
     dec_s[c] = lp;
     psi_s[c] = ps;
@@ -208,7 +220,7 @@ __global__ __launch_bounds__(SEL_NT) void select_kernel(int n, int V, int P, int
     if (lane == 0) {
       const int j = cand[c];
       const float ps = psi_s[c];
-      const float inc = __fsub_rn(ps, prefix[h]);
+      const float inc = sub_rn(ps, prefix[h]);
       rec_i[b * 4 + 0] = h; rec_i[b * 4 + 1] = j; rec_i[b * 4 + 2] = k; rec_i[b * 4 + 3] = none;
       rec_f[b * 4 + 0] = best.v; rec_f[b * 4 + 1] = dec_s[c]; rec_f[b * 4 + 2] = inc; rec_f[b * 4 + 3] = ps;
       last_next[b] = j;
