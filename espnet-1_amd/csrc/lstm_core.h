@@ -1,5 +1,6 @@
-// The weight-stream core of the three LSTM kernels: lstm_step_kernel (rnn_lm.hip),
-// lstm_cell_fwd_kernel and lstm_cell_bwd_kernel (lstm_train.hip).
+// The weight-stream core of the LSTM kernels: lstm_step_kernel (rnn_lm.hip), lstm_cell_fwd_kernel
+// and lstm_cell_bwd_kernel (lstm_train.hip), and their two-direction, length-masked forms
+// lstm_bicell_fwd_kernel and lstm_bicell_bwd_kernel (lstm_bidir.hip).
 //
 // A launch is rows (n hypotheses or a training batch) x a packed weight: a few MFMAs per 16-B
 // weight load.  A block owns MT 16-row tiles (up to 64 rows) x NJ 16-row weight tiles and ALL of
@@ -210,18 +211,34 @@ EA_DEV void zero_pad(int r0, int n, int c0, long ld, float* a, float* b, bf16* h
   }
 }
 
+// Row masks of the cell epilogues.  AllRows: every row of the launch takes the cell update (the
+// test folds away).  A mask whose operator()(row) is false makes the epilogue store zeros for
+// that row in place of the update (lstm_bidir.hip: the frames past a sequence's length).
+struct AllRows {
+  EA_DEV bool operator()(int) const { return true; }
+};
+
 // The forward cell update on block_product's sums, a tile being 4 hidden units x the 4 gates
 // (torch order i, f, g, o): gates = sums + add(row, unit) (a float4), c = sigmoid(f) *
 // cprev(row, unit) + sigmoid(i) * tanh(g), h = sigmoid(o) * tanh(c).  Stores h, c, the bf16 h
 // (hb or NULL) and the four activated gates (gates or NULL) and zeroes the pad columns [H, ldo).
-template <int MT, int NJ, class Add, class CPrev>
+// Rows with !active(row) store h = c = 0 and zero gates.
+template <int MT, int NJ, class Add, class CPrev, class Active>
 EA_DEV void cell_fwd_epilogue(const float (*red)[16 * MT][16 * NJ + 4], int r0, int t0, int n, int H, const Add& add,
-                              const CPrev& cprev, float* ho, float* co, bf16* hb, long ldo, float* gates, long ldg) {
+                              const CPrev& cprev, float* ho, float* co, bf16* hb, long ldo, float* gates, long ldg,
+                              const Active& active) {
   constexpr int CELLS = 16 * MT * NJ * 4;  // (row, hidden unit) pairs of the block
   for (int ci = threadIdx.x; ci < CELLS; ci += 64 * NW) {
     const int lrow = ci / (NJ * 4), cu = ci % (NJ * 4);  // cu = 4 * (tile in block) + unit in tile
     const int row = r0 + lrow, unit = t0 * 4 + cu;
     if (row >= n || unit >= H) continue;
+    if (!active(row)) {
+      co[(long)row * ldo + unit] = 0.f;
+      ho[(long)row * ldo + unit] = 0.f;
+      if (hb) hb[(long)row * ldo + unit] = (bf16)0.f;
+      if (gates) *(float4*)(gates + (long)row * ldg + 4 * unit) = make_float4(0.f, 0.f, 0.f, 0.f);
+      continue;
+    }
     const float4 s = sum_partials<float4>(red, lrow, cu * 4);
     const float4 ad = add(row, unit);
     const float cp = cprev(row, unit);
@@ -236,14 +253,72 @@ EA_DEV void cell_fwd_epilogue(const float (*red)[16 * MT][16 * NJ + 4], int r0, 
   }
   zero_pad<16 * MT>(r0, n, H, ldo, ho, co, hb);
 }
+template <int MT, int NJ, class Add, class CPrev>
+EA_DEV void cell_fwd_epilogue(const float (*red)[16 * MT][16 * NJ + 4], int r0, int t0, int n, int H, const Add& add,
+                              const CPrev& cprev, float* ho, float* co, bf16* hb, long ldo, float* gates, long ldg) {
+  cell_fwd_epilogue<MT, NJ>(red, r0, t0, n, H, add, cprev, ho, co, hb, ldo, gates, ldg, AllRows{});
+}
+
+// The backward cell update of the block's 16 hidden units (column tile t0) on block_product's
+// sums: dh = dh_out + the sums (`rec`: block-uniform, false = no recurrent term yet), then the
+// cell's gradient (ea_lstm_cell_bwd in include/espnet_amd.h).  P names one step's operands: n, H,
+// G = 4H, dho / lddh, gates / ldg, c, cprev / ldc, dci, dco / lddc, dg, dgb / ldd, dht / ldt.
+// Stores dgates (torch gate order), their bf16 copy (dgb or NULL), the carry dc_out and dh (dht or
+// NULL) and zeroes the pad columns [4H, ldd) of dgates and [H, lddc) of the carry.  Rows with
+// !active(row) store zero dgates and a zero carry.
+template <int MT, class P, class Active>
+EA_DEV void cell_bwd_epilogue(const float (*red)[16 * MT][16 + 4], bool rec, int r0, int t0, const P& p,
+                              const Active& active) {
+  constexpr int CELLS = 16 * MT * 16;
+  for (int ci = threadIdx.x; ci < CELLS; ci += 64 * NW) {
+    const int lrow = ci / 16, cu = ci % 16;
+    const int row = r0 + lrow, unit = t0 * 16 + cu;
+    if (row >= p.n || unit >= p.H) continue;
+    if (!active(row)) {
+      float* o = p.dg + (long)row * p.ldd + unit;
+      p.dco[(long)row * p.lddc + unit] = 0.f;
+      o[0] = 0.f; o[p.H] = 0.f; o[2 * (long)p.H] = 0.f; o[3 * (long)p.H] = 0.f;
+      if (p.dgb) {
+        bf16* ob = p.dgb + (long)row * p.ldd + unit;
+        ob[0] = (bf16)0.f; ob[p.H] = (bf16)0.f; ob[2 * (long)p.H] = (bf16)0.f; ob[3 * (long)p.H] = (bf16)0.f;
+      }
+      if (p.dht) p.dht[(long)row * p.ldt + unit] = 0.f;
+      continue;
+    }
+    float dh = p.dho ? p.dho[(long)row * p.lddh + unit] : 0.f;
+    if (rec) dh += sum_partials<float>(red, lrow, cu);
+    const float4 a = *(const float4*)(p.gates + (long)row * p.ldg + 4 * unit);  // i, f, g, o
+    const float tc = tanhf(p.c[(long)row * p.ldc + unit]);
+    const float cp = p.cprev[(long)row * p.ldc + unit];
+    const float dcar = p.dci ? p.dci[(long)row * p.lddc + unit] : 0.f;
+    const float d_o = dh * tc * a.w * (1.f - a.w);
+    const float dc = dcar + dh * a.w * (1.f - tc * tc);
+    const float d_i = dc * a.z * a.x * (1.f - a.x);
+    const float d_f = dc * cp * a.y * (1.f - a.y);
+    const float d_g = dc * a.x * (1.f - a.z * a.z);
+    p.dco[(long)row * p.lddc + unit] = dc * a.y;
+    float* o = p.dg + (long)row * p.ldd + unit;  // torch gate order: column gate * H + unit
+    o[0] = d_i; o[p.H] = d_f; o[2 * (long)p.H] = d_g; o[3 * (long)p.H] = d_o;
+    if (p.dgb) {
+      bf16* ob = p.dgb + (long)row * p.ldd + unit;
+      ob[0] = (bf16)d_i; ob[p.H] = (bf16)d_f; ob[2 * (long)p.H] = (bf16)d_g; ob[3 * (long)p.H] = (bf16)d_o;
+    }
+    if (p.dht) p.dht[(long)row * p.ldt + unit] = dh;
+  }
+
+  // pad columns [4H, ldd) of dgates and [H, lddc) of the carry
+  zero_pad<16 * MT>(r0, p.n, p.G, p.ldd, p.dg, nullptr, p.dgb);
+  zero_pad<16 * MT>(r0, p.n, p.H, p.lddc, p.dco, nullptr, nullptr);
+}
 
 // Row-tile dispatch: MT = 1 / 2 / 4 row tiles per block for n <= 16 / <= 32 / more, NJ = 2 column
 // tiles per block when `wide`, U = 8 slices in flight (4 with MT = 4).  kern(Int<MT>, Int<NJ>,
-// Int<U>) names the instantiation; ctiles = the column tiles of the launch.
+// Int<U>) names the instantiation; ctiles = the column tiles of the launch, nz = its grid.z (the
+// directions of lstm_bidir.hip).
 template <class P, class Kern>
-int launch_tiles(int n, int ctiles, bool wide, const P& p, hipStream_t st, Kern kern) {
+int launch_tiles(int n, int ctiles, bool wide, const P& p, hipStream_t st, Kern kern, int nz = 1) {
   auto go = [&](auto mt, auto nj) {
-    const dim3 grid(ea_cdiv(ctiles, nj()), ea_cdiv(n, 16 * mt()), 1);
+    const dim3 grid(ea_cdiv(ctiles, nj()), ea_cdiv(n, 16 * mt()), nz);
     hipLaunchKernelGGL(kern(mt, nj, Int<(mt() == 4 ? 4 : 8)>()), grid, dim3(64 * NW), 0, st, p);
     EA_LAUNCH_CHECK();
     return 0;

@@ -15,8 +15,8 @@
 //
 // Both run on lstm_core.h's block product with B a training batch.  The forward's column tile
 // is 4 hidden units x 4 gates (so the cell update is local to the tile and is the decoding
-// step's), the backward's is 16 hidden units with a cell-gradient epilogue of its own.  The
-// time loop is the host's.
+// step's), the backward's is 16 hidden units with the cell-gradient epilogue (both epilogues are
+// lstm_core.h's, shared with lstm_bidir.hip).  The time loop is the host's.
 #include "lstm_core.h"
 
 namespace {
@@ -102,35 +102,7 @@ __global__ __launch_bounds__(64 * NW) void lstm_cell_bwd_kernel(CellBwdP p) {
     block_product<BF, MT, 1, U>(a, p.wt, Gp / (BF ? 32 : 16), t0, (p.H + 15) / 16, red);
   }
 
-  constexpr int CELLS = 16 * MT * 16;
-  for (int ci = threadIdx.x; ci < CELLS; ci += 64 * NW) {
-    const int lrow = ci / 16, cu = ci % 16;
-    const int row = r0 + lrow, unit = t0 * 16 + cu;
-    if (row >= p.n || unit >= p.H) continue;
-    float dh = p.dho ? p.dho[(long)row * p.lddh + unit] : 0.f;
-    if (rec) dh += sum_partials<float>(red, lrow, cu);
-    const float4 a = *(const float4*)(p.gates + (long)row * p.ldg + 4 * unit);  // i, f, g, o
-    const float tc = tanhf(p.c[(long)row * p.ldc + unit]);
-    const float cp = p.cprev[(long)row * p.ldc + unit];
-    const float dcar = p.dci ? p.dci[(long)row * p.lddc + unit] : 0.f;
-    const float d_o = dh * tc * a.w * (1.f - a.w);
-    const float dc = dcar + dh * a.w * (1.f - tc * tc);
-    const float d_i = dc * a.z * a.x * (1.f - a.x);
-    const float d_f = dc * cp * a.y * (1.f - a.y);
-    const float d_g = dc * a.x * (1.f - a.z * a.z);
-    p.dco[(long)row * p.lddc + unit] = dc * a.y;
-    float* o = p.dg + (long)row * p.ldd + unit;  // torch gate order: column gate * H + unit
-    o[0] = d_i; o[p.H] = d_f; o[2 * (long)p.H] = d_g; o[3 * (long)p.H] = d_o;
-    if (p.dgb) {
-      bf16* ob = p.dgb + (long)row * p.ldd + unit;
-      ob[0] = (bf16)d_i; ob[p.H] = (bf16)d_f; ob[2 * (long)p.H] = (bf16)d_g; ob[3 * (long)p.H] = (bf16)d_o;
-    }
-    if (p.dht) p.dht[(long)row * p.ldt + unit] = dh;
-  }
-
-  // pad columns [4H, ldd) of dgates and [H, lddc) of the carry
-  zero_pad<16 * MT>(r0, p.n, p.G, p.ldd, p.dg, nullptr, p.dgb);
-  zero_pad<16 * MT>(r0, p.n, p.H, p.lddc, p.dco, nullptr, nullptr);
+  cell_bwd_epilogue<MT>(red, rec, r0, t0, p, AllRows{});
 }
 
 }  // namespace

@@ -6,7 +6,9 @@ its arena: an LSTMLayer per layer (from (nn.LSTM, k) or an nn.LSTMCell), an Embe
 LinearHead.  A handle holds the module's own Parameters (their .grad is the arena's gradient
 view), the compute-dtype view of its matrix and what the kernels' ABI derives from them.  The
 recurrence itself (state buffers, the cell kernels' argument lists, the weight-gradient tail) is
-LSTMTape's, shared by LSTMLayerFn and the decoder's attention + layer 0 node.
+LSTMTape's, shared by LSTMLayerFn and the decoder's attention + layer 0 node.  BiLSTMTape /
+BiLSTMLayerFn are the same for the encoder's layers: one or two directions per launch over rows
+of unequal lengths (ea_lstm_bicell_fwd / ea_lstm_bicell_bwd).
 
 Rows are time-major inside the path (row t * B + b), so the slice of one time step is a
 contiguous (B, .) block for ea_lstm_cell_fwd / ea_lstm_cell_bwd and every product that is not
@@ -17,13 +19,19 @@ into the arena's gradient views (Parameter.grad), as every other node of the pac
 """
 from __future__ import annotations
 
+import ctypes
+from types import SimpleNamespace
+
 import torch
 
 from .. import hip_ops as ops
-from .._lib import BF16, F32, lib
+from .._lib import BF16, ENUMS, F32, lib
 from .lstm_pack import HHPacks, rup
 
 EMBED_BWD_ROWS = 4096  # ea_embed_bwd stages the ids of one call in LDS
+# the operand-block indices of ea_lstm_bicell_fwd / ea_lstm_bicell_bwd (EA_BIF_* / EA_BIB_* of the header)
+_BIF = SimpleNamespace(**{k[7:]: v for k, v in ENUMS.items() if k.startswith("EA_BIF_")})
+_BIB = SimpleNamespace(**{k[7:]: v for k, v in ENUMS.items() if k.startswith("EA_BIB_")})
 
 
 def f32c(t: torch.Tensor) -> torch.Tensor:
@@ -57,10 +65,13 @@ class LinearHead:
 class LSTMLayer:
     """One LSTM layer for the recurrent kernels: the four Parameters of nn.LSTM's layer k or of an
     nn.LSTMCell (k None), w_ih = weight_ih in the compute dtype cd (an arena view), the HHPacks of
-    weight_hh, and the sizes and dtype code of the cell kernels' ABI."""
+    weight_hh, and the sizes and dtype code of the cell kernels' ABI.  reverse: the `_reverse`
+    parameters of a bidirectional nn.LSTM's layer k."""
 
-    def __init__(self, module, w_ih: torch.Tensor, cd, k: int = None):
-        sfx = "" if k is None else f"_l{k}"
+    def __init__(self, module, w_ih: torch.Tensor, cd, k: int = None, reverse: bool = False):
+        if reverse and k is None:
+            raise ValueError("reverse names the second direction of an nn.LSTM layer: give k")
+        sfx = ("" if k is None else f"_l{k}") + ("_reverse" if reverse else "")
         self.weight_ih, self.weight_hh = getattr(module, "weight_ih" + sfx), getattr(module, "weight_hh" + sfx)
         self.bias_ih, self.bias_hh = getattr(module, "bias_ih" + sfx), getattr(module, "bias_hh" + sfx)
         self.w_ih, self.cd = w_ih, cd
@@ -260,6 +271,187 @@ class LSTMLayerFn(torch.autograd.Function):
             ops.linear_dx(dgm, layer.w_ih, dx)
         tape.weight_grads(xc)
         return dx, None, None, None, None, None
+
+
+class BiLSTMTape:
+    """The recurrence of one layer's ndir = len(layers) directions (1, or 2: forward and reverse)
+    over T steps of B rows of unequal lengths `lens` (B int64 on the device), on
+    ea_lstm_bicell_fwd / ea_lstm_bicell_bwd: ONE launch per step carries both directions.
+
+    Every direction owns its buffers (the kernels also write the pad columns of a state row, so
+    the directions share none): hs / cs (T + 1, B, Hp) f32, hb = hs in bf16 under amp, gates
+    (T, B, 4H); for the backward dg / dgb (T, B, ldd) and the carry dc (T, B, Hp).  Direction 0
+    keeps its initial state in slot 0 and h_t in slot t + 1; direction 1 keeps its initial state
+    in slot T and h_t in slot t.  Both initial slots are zero; every other slot is written by the
+    sweep, zeros where t >= lens[b].  The operand blocks hold slot-0 addresses and step strides;
+    a step changes only t (and `first`)."""
+
+    def __init__(self, layers, lens: torch.Tensor, T: int, B: int, dev):
+        lay = layers[0]
+        if len(layers) not in (1, 2) or any((l.H, l.cd) != (lay.H, lay.cd) for l in layers):
+            raise ValueError("one or two LSTMLayers of one size and dtype")
+        if lens.dtype != torch.long or lens.numel() != B or not lens.is_contiguous():
+            raise ValueError(f"lens: {B} int64 lengths on the device")
+        self.layers, self.lens, self.T, self.B, self.ndir = layers, lens, T, B, len(layers)
+        Hp, bf = lay.Hp, lay.bf
+        self.hs, self.cs, self.hb, self.gates = [], [], [], []
+        for d in range(self.ndir):
+            hs = torch.empty(T + 1, B, Hp, device=dev)
+            cs = torch.empty(T + 1, B, Hp, device=dev)
+            hb = torch.empty(T + 1, B, Hp, dtype=torch.bfloat16, device=dev) if bf else None
+            init = T if d else 0
+            hs[init].zero_()
+            cs[init].zero_()
+            if bf:
+                hb[init].zero_()
+            self.hs.append(hs)
+            self.cs.append(cs)
+            self.hb.append(hb)
+            self.gates.append(torch.empty(T, B, lay.G, device=dev))
+        self.hin = self.hb if bf else self.hs
+
+    def forward(self, xproj):
+        """The forward sweep on xproj[d] (T * B, 4H), the input projection of direction d."""
+        lay, T, B, ndir = self.layers[0], self.T, self.B, self.ndir
+        H, Hp, G, bf = lay.H, lay.Hp, lay.G, lay.bf
+        ptrs, strides = (ctypes.c_void_p * (2 * _BIF.NPTR))(), (ctypes.c_long * (2 * _BIF.NSTR))()
+        tt = (ctypes.c_int * 2)()
+        for d in range(ndir):
+            xp = xproj[d]
+            if xp.shape != (T * B, G) or xp.stride() != (G, 1):
+                raise ValueError(f"xproj {tuple(xp.shape)} for {T} steps of {B} rows")
+            hin, hs, cs, hb = self.hin[d], self.hs[d], self.cs[d], self.hb[d]
+            prev, out = (1, 0) if d else (0, 1)  # the slot of t's previous / new state, at t = 0
+            q, s = d * _BIF.NPTR, d * _BIF.NSTR
+            ptrs[q + _BIF.WPACK] = self.layers[d].hh.fwd.data_ptr()
+            ptrs[q + _BIF.XPROJ] = xp.data_ptr()
+            ptrs[q + _BIF.H_PREV], ptrs[q + _BIF.C_PREV] = hin[prev].data_ptr(), cs[prev].data_ptr()
+            ptrs[q + _BIF.H_OUT], ptrs[q + _BIF.C_OUT] = hs[out].data_ptr(), cs[out].data_ptr()
+            ptrs[q + _BIF.HB_OUT] = hb[out].data_ptr() if bf else None
+            ptrs[q + _BIF.GATES] = self.gates[d].data_ptr()
+            for i, v in ((_BIF.LDX, G), (_BIF.SX, B * G), (_BIF.LDS, Hp), (_BIF.SS, B * Hp), (_BIF.LDG, G),
+                         (_BIF.SG, B * G)):
+                strides[s + i] = v
+        wd, lens, st = lay.wd, self.lens.data_ptr(), ops.stream()
+        for s in range(T):
+            tt[0], tt[1] = s, T - 1 - s
+            lib.ea_lstm_bicell_fwd(wd, ndir, B, H, lens, ptrs, strides, tt, st)
+
+    def outputs(self) -> torch.Tensor:
+        """h of every step, the directions side by side: a new (T * B, ndir * H) f32 tensor (a
+        concat copy: the next GEMM reads one operand)."""
+        H, TB = self.layers[0].H, self.T * self.B
+        y = torch.empty(TB, self.ndir * H, device=self.hs[0].device)
+        for d in range(self.ndir):
+            hs = self.hs[d][:self.T] if d else self.hs[d][1:]
+            y[:, d * H:(d + 1) * H].copy_(hs.view(TB, -1)[:, :H])
+        return y
+
+    def backward(self, dy: torch.Tensor):
+        """The backward sweep on dy (T * B, ndir * H) f32 contiguous; leaves every step's gate
+        gradients in dg[d] (dgm[d]: their (T * B, 4H) view in the compute dtype)."""
+        lay, T, B, ndir = self.layers[0], self.T, self.B, self.ndir
+        H, Hp, G, ldd, bf = lay.H, lay.Hp, lay.G, lay.ldd, lay.bf
+        dev = dy.device
+        if dy.shape != (T * B, ndir * H) or not dy.is_contiguous() or dy.dtype != torch.float32:
+            raise ValueError(f"dy {tuple(dy.shape)} for {T} steps of {B} rows, {ndir} directions")
+        self.dg, self.dgm, keep = [], [], []
+        ptrs, strides = (ctypes.c_void_p * (2 * _BIB.NPTR))(), (ctypes.c_long * (2 * _BIB.NSTR))()
+        tt, first = (ctypes.c_int * 2)(), (ctypes.c_int * 2)()
+        for d in range(ndir):
+            dg = torch.empty(T, B, ldd, device=dev)
+            dgb = torch.empty(T, B, ldd, dtype=torch.bfloat16, device=dev) if bf else None
+            dc = torch.empty(T, B, Hp, device=dev)
+            dgn = dgb if bf else dg
+            self.dg.append(dg)
+            self.dgm.append(dgn.view(T * B, ldd)[:, :G])
+            keep.append(dc)
+            cs, q, s = self.cs[d], d * _BIB.NPTR, d * _BIB.NSTR
+            nxt = -1 if d else 1  # the step this direction's sweep ran before t, relative to t
+            ptrs[q + _BIB.WPACK_T] = self.layers[d].hh.bwd.data_ptr()
+            ptrs[q + _BIB.DGATES_NEXT] = dgn.data_ptr() + nxt * B * ldd * dgn.element_size()
+            ptrs[q + _BIB.DH_OUT] = dy.data_ptr() + d * H * 4
+            ptrs[q + _BIB.GATES] = self.gates[d].data_ptr()
+            ptrs[q + _BIB.C], ptrs[q + _BIB.C_PREV] = (cs[0].data_ptr(), cs[1].data_ptr()) if d else (cs[1].data_ptr(),
+                                                                                                    cs[0].data_ptr())
+            ptrs[q + _BIB.DC_IN] = dc.data_ptr() + nxt * B * Hp * 4
+            ptrs[q + _BIB.DC_OUT] = dc.data_ptr()
+            ptrs[q + _BIB.DGATES] = dg.data_ptr()
+            ptrs[q + _BIB.DGATES_B] = dgb.data_ptr() if bf else None
+            for i, v in ((_BIB.LDD, ldd), (_BIB.SD, B * ldd), (_BIB.LDDH, ndir * H), (_BIB.SDH, B * ndir * H),
+                         (_BIB.LDG, G), (_BIB.SG, B * G), (_BIB.LDC, Hp), (_BIB.SC, B * Hp), (_BIB.LDDC, Hp),
+                         (_BIB.SDC, B * Hp)):
+                strides[s + i] = v
+        wd, lens, st = lay.wd, self.lens.data_ptr(), ops.stream()
+        for s in range(T):
+            tt[0], tt[1] = T - 1 - s, s
+            first[0] = first[1] = int(s == 0)
+            lib.ea_lstm_bicell_bwd(wd, ndir, B, H, lens, ptrs, strides, tt, first, st)
+        del keep  # the launches are stream ordered: the allocator reuses dc only after them
+
+    def weight_grads(self, x: torch.Tensor):
+        """Every direction's four parameter gradients from dgm and the input rows x (T * B, I)
+        in the compute dtype, as LSTMTape.weight_grads."""
+        TB = self.T * self.B
+        for d, lay in enumerate(self.layers):
+            hin = self.hin[d][1:] if d else self.hin[d][:self.T]
+            hprev = hin.view(TB, lay.Hp)[:, :lay.H]
+            ops.linear_dw(self.dgm[d], x, lay.weight_ih.grad, accumulate=True)
+            ops.linear_dw(self.dgm[d], hprev, lay.weight_hh.grad, accumulate=True)
+            dg32 = self.dg[d].view(TB, lay.ldd)[:, :lay.G]
+            ops.colsum(dg32, lay.bias_ih.grad, accumulate=True)
+            ops.colsum(dg32, lay.bias_hh.grad, accumulate=True)
+
+
+class BiLSTMLayerFn(torch.autograd.Function):
+    """One (bi)directional LSTM layer over (T, B) rows of lengths lens, torch.nn.LSTM on a
+    pack_padded_sequence: x (T*B, I) f32 -> (T*B, ndir*H) f32, [forward | reverse], rows at
+    t >= lens[b] exactly 0.  layers: the LSTMLayer of each direction.  Zero initial states.
+    anchor (a tensor that requires grad, or None) keeps the node in the graph when x, the features
+    of the first layer, does not require grad."""
+
+    @staticmethod
+    def forward(ctx, x, layers, lens, T, B, anchor=None):
+        xc = ops.cast(x, layers[0].cd)
+        xproj = [lay.input_proj(xc, lay.w_ih, lay.bias_sum()) for lay in layers]
+        tape = BiLSTMTape(layers, lens, T, B, x.device)
+        tape.forward(xproj)
+        ctx.save = (tape, xc)
+        return tape.outputs()
+
+    @staticmethod
+    def backward(ctx, dy):
+        tape, xc = ctx.save
+        ctx.save = None
+        tape.backward(f32c(dy).contiguous())
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty(xc.shape[0], tape.layers[0].I, device=dy.device)
+            for d, lay in enumerate(tape.layers):
+                ops.linear_dx(tape.dgm[d], lay.w_ih, dx, epi=ops.make_epi(beta=1.0) if d else None)
+        tape.weight_grads(xc)
+        return dx, None, None, None, None, None
+
+
+class TanhFn(torch.autograd.Function):
+    """tanh on ea_tanh_fwd / ea_tanh_bwd, f32."""
+
+    @staticmethod
+    def forward(ctx, x):
+        x = f32c(x).contiguous()
+        y = torch.empty_like(x)
+        lib.ea_tanh_fwd(x.numel(), x.data_ptr(), y.data_ptr(), ops.stream())
+        ctx.save = y
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        y = ctx.save
+        ctx.save = None
+        dy = f32c(dy).contiguous()
+        dx = torch.empty_like(y)
+        lib.ea_tanh_bwd(y.numel(), y.data_ptr(), dy.data_ptr(), dx.data_ptr(), ops.stream())
+        return dx
 
 
 class OutLinearFn(torch.autograd.Function):

@@ -25,6 +25,7 @@ from ..asr.decoder.rnn_decoder import RNNDecoder
 from ..asr.decoder.transformer_decoder import AbsDecoder, TransformerDecoder
 from ..asr.encoder.conformer_encoder import AbsEncoder, ConformerEncoder
 from ..asr.encoder.e_branchformer_encoder import EBranchformerEncoder
+from ..asr.encoder.rnn_encoder import RNNEncoder
 from ..asr.encoder.transformer_encoder import TransformerEncoder
 from ..asr.espnet_model import AbsESPnetModel, ESPnetASRModel, UtteranceMVN
 from ..asr.frontend.default import DefaultFrontend, GlobalMVN
@@ -42,7 +43,7 @@ normalize_choices = ClassChoices("normalize", dict(global_mvn=GlobalMVN, utteran
                                  type_check=AbsNormalize, default="utterance_mvn", optional=True)
 model_choices = ClassChoices("model", dict(espnet=ESPnetASRModel), type_check=AbsESPnetModel, default="espnet")
 encoder_choices = ClassChoices("encoder", dict(conformer=ConformerEncoder, transformer=TransformerEncoder,
-                                               e_branchformer=EBranchformerEncoder),
+                                               e_branchformer=EBranchformerEncoder, rnn=RNNEncoder),
                                type_check=AbsEncoder, default="rnn")
 decoder_choices = ClassChoices("decoder", dict(transformer=TransformerDecoder, rnn=RNNDecoder), type_check=AbsDecoder,
                                default=None, optional=True)

@@ -188,8 +188,9 @@ class CapturedTrainStep:
                 F = m.frontend.output_size()
                 lens_host = [int(m.frontend.stft.frames_lens(int(v))) for v in lens_host]
             m.specaug.predraw(B, T, F, lens_host, m._device)
-        if not getattr(m.encoder, "interctc_layer_idx", None):
-            # (an encoder with intermediate-CTC taps loops over its layers itself and draws nothing)
+        if not getattr(m.encoder, "interctc_layer_idx", None) and getattr(m.encoder, "encoders", None) is not None:
+            # (an encoder with intermediate-CTC taps loops over its layers itself and draws nothing;
+            # the RNN encoder has no MultiSequential)
             layerdrop_draw(len(m.encoder.encoders))
         if getattr(m.decoder, "decoders", None) is not None:  # (the RNN decoder has no MultiSequential)
             layerdrop_draw(len(m.decoder.decoders))

@@ -924,6 +924,60 @@ int ea_lstm_cell_bwd(int wdtype, int n, int H, const void* wpack_t, const void* 
                      const float* c_prev, long ldc, const float* dc_in, float* dc_out, long lddc,
                      float* dgates, void* dgates_b, long ldd, float* dh_tot, long ldt, void* stream);
 
+/* ---------------------------------------------------------------- RNNEncoder (BLSTM / BLSTMP) */
+
+/* One time step of ndir (1 or 2) independent LSTM directions over n rows of unequal lengths, in
+ * one launch (grid.z = direction): torch.nn.LSTM on a pack_padded_sequence, unrolled by the host.
+ * Each direction has its own operand block.  Every pointer of a block is the address of sweep
+ * slot 0; the kernel adds t * (its step stride), so a sweep changes only t (and `first`) between
+ * launches.  At step s of a forward sweep the host passes t = s for direction 0 and t = T-1-s
+ * for direction 1, in the backward sweep t = T-1-s and t = s; which slot holds the "previous"
+ * state of a direction is folded into its base pointers (direction 1: h_prev = slot t+1).
+ *
+ * lens (n int64, device memory, shared by the directions): row r is ACTIVE in direction d iff
+ * t_d < lens[r].  An active row computes exactly what ea_lstm_cell_fwd / ea_lstm_cell_bwd
+ * compute (same block product, same epilogue, bit for bit).  An inactive row stores zeros:
+ * forward h_out = c_out = 0, hb_out = 0, gates = 0; backward dgates = 0, dgates_b = 0,
+ * dc_out = 0.  With zero initial slots this is pack_padded_sequence's recurrence for any order
+ * of lengths (no sorting), lengths of 0 included: the reverse direction of row r enters frame
+ * lens[r]-1 from a zero state, the gradient entering a row's last frame is zero, padded outputs
+ * and the gate gradients of padded steps are exactly 0.
+ *
+ * n, H, wdtype, the packs, the gate layouts and the pad columns are ea_lstm_cell_*'s.  The two
+ * directions must not share any written buffer (the pad columns [H, lds) of a state row are
+ * written too).  All strides are in elements of the pointed-to type.
+ *
+ * The operand block of direction d is ptrs[d * NPTR .. ], strides[d * NSTR .. ] and t[d] (host
+ * arrays, read before the launch), indexed by the enumerators below.
+ * ea_lstm_bicell_fwd (NPTR = EA_BIF_NPTR, NSTR = EA_BIF_NSTR):  XPROJ (row stride LDX >= 4H, step
+ *   stride SX);  H_PREV (f32; bf16 with EA_BF16), C_PREV, H_OUT, C_OUT, HB_OUT (bf16, required
+ *   with EA_BF16, else NULL or given): row stride LDS >= H, step stride SS;  GATES (LDG >= 4H,
+ *   LDG % 4 == 0, 16-B aligned, SG % 4 == 0), step stride SG.
+ * ea_lstm_bicell_bwd (NPTR = EA_BIB_NPTR, NSTR = EA_BIB_NSTR):  DGATES_NEXT (the dgates / dgates_b
+ *   of the step this direction ran before: the same buffer shifted by one step), DGATES, DGATES_B:
+ *   row stride LDD >= 4H, step stride SD;  DH_OUT (or NULL = 0): LDDH, SDH;  GATES: LDG, SG;
+ *   C, C_PREV: LDC, SC;  DC_IN, DC_OUT (the carry, one slot per step, DC_IN = the slot of the
+ *   step before): LDDC, SDC.  first[d] != 0: no recurrent term yet: DGATES_NEXT and DC_IN are
+ *   not read (the direction's first backward step). */
+enum { EA_BIF_WPACK = 0, EA_BIF_XPROJ = 1, EA_BIF_H_PREV = 2, EA_BIF_C_PREV = 3, EA_BIF_H_OUT = 4,
+       EA_BIF_C_OUT = 5, EA_BIF_HB_OUT = 6, EA_BIF_GATES = 7, EA_BIF_NPTR = 8 };
+enum { EA_BIF_LDX = 0, EA_BIF_SX = 1, EA_BIF_LDS = 2, EA_BIF_SS = 3, EA_BIF_LDG = 4, EA_BIF_SG = 5,
+       EA_BIF_NSTR = 6 };
+enum { EA_BIB_WPACK_T = 0, EA_BIB_DGATES_NEXT = 1, EA_BIB_DH_OUT = 2, EA_BIB_GATES = 3, EA_BIB_C = 4,
+       EA_BIB_C_PREV = 5, EA_BIB_DC_IN = 6, EA_BIB_DC_OUT = 7, EA_BIB_DGATES = 8, EA_BIB_DGATES_B = 9,
+       EA_BIB_NPTR = 10 };
+enum { EA_BIB_LDD = 0, EA_BIB_SD = 1, EA_BIB_LDDH = 2, EA_BIB_SDH = 3, EA_BIB_LDG = 4, EA_BIB_SG = 5,
+       EA_BIB_LDC = 6, EA_BIB_SC = 7, EA_BIB_LDDC = 8, EA_BIB_SDC = 9, EA_BIB_NSTR = 10 };
+int ea_lstm_bicell_fwd(int wdtype, int ndir, int n, int H, const long long* lens, const void* const* ptrs,
+                       const long* strides, const int* t, void* stream);
+int ea_lstm_bicell_bwd(int wdtype, int ndir, int n, int H, const long long* lens, const void* const* ptrs,
+                       const long* strides, const int* t, const int* first, void* stream);
+
+/* y = tanh(x) and dx = dy (1 - y^2) over n f32 elements (the RNNP / RNN projection's activation;
+ * tanhf, as torch.tanh on f32).  dx may alias dy. */
+int ea_tanh_fwd(long n, const float* x, float* y, void* stream);
+int ea_tanh_bwd(long n, const float* y, const float* dy, float* dx, void* stream);
+
 /* ---------------------------------------------------------------- RNNDecoder (location attention) */
 
 /* One step of the location-aware attention AttLoc (espnet/nets/pytorch_backend/rnn/attentions.py:
