@@ -16,33 +16,12 @@ from typing import List, Optional, Tuple, Union
 import torch
 from torch import nn
 
-from ...layers.common import LayerNormFn, multisequential_draw, site_seed
+from ...layers.common import LayerNormFn
 from ...layers.conformer import (ConvolutionModule, EncoderLayer, LayerNorm,
                                  PositionwiseFeedForward, RelPositionMultiHeadedAttention)
 from ...layers.interctc import InterCTCTapFn, TapState
 from ...layers.subsampling import Conv2dSubsampling, LegacyRelPositionalEncoding, RelPositionalEncoding
-from ... import hip_ops as ops
-from ..._lib import lib
-
-
-class TooShortUttError(Exception):
-    """subsampling.py:14-28"""
-
-    def __init__(self, message, actual_size, limit):
-        super().__init__(message)
-        self.actual_size = actual_size
-        self.limit = limit
-
-
-class AbsEncoder(nn.Module):
-    def output_size(self) -> int:
-        raise NotImplementedError
-
-
-class _AfterNorm(nn.LayerNorm):
-    def bind(self, arena, prefix, cd):
-        from ...layers.common import Bound
-        self._b = Bound(arena, prefix, cd)
+from .abs_encoder import INPUT_LAYERS, AfterNorm, SubsamplingEncoder, resolve_rel_pos_type
 
 
 class ConditioningLayer(nn.Linear):
@@ -56,7 +35,9 @@ class ConditioningLayer(nn.Linear):
         self._b = Bound(arena, prefix, cd)
 
 
-class ConformerEncoder(AbsEncoder):
+class ConformerEncoder(SubsamplingEncoder):
+    layer_class = EncoderLayer
+
     def __init__(
         self,
         input_size: int,
@@ -90,22 +71,13 @@ class ConformerEncoder(AbsEncoder):
         super().__init__()
         self._output_size = output_size
         # option resolution as conformer_encoder.py:117-143
-        if rel_pos_type == "legacy":
-            if pos_enc_layer_type == "rel_pos":
-                pos_enc_layer_type = "legacy_rel_pos"
-            if selfattention_layer_type == "rel_selfattn":
-                selfattention_layer_type = "legacy_rel_selfattn"
-        elif rel_pos_type == "latest":
-            assert selfattention_layer_type != "legacy_rel_selfattn"
-            assert pos_enc_layer_type != "legacy_rel_pos"
-        else:
-            raise ValueError("unknown rel_pos_type: " + rel_pos_type)
+        pos_enc_layer_type, selfattention_layer_type = resolve_rel_pos_type(
+            rel_pos_type, pos_enc_layer_type, selfattention_layer_type)
         if pos_enc_layer_type not in ("abs_pos", "scaled_abs_pos", "rel_pos", "legacy_rel_pos"):
             raise ValueError("unknown pos_enc_layer: " + pos_enc_layer_type)
         if selfattention_layer_type not in ("selfattn", "legacy_rel_selfattn", "rel_selfattn"):
             raise ValueError("unknown encoder_attn_layer: " + selfattention_layer_type)
-        if input_layer not in ("linear", "conv2d", "conv2d1", "conv2d2", "conv2d6", "conv2d8",
-                               "embed") and not isinstance(input_layer, nn.Module) and input_layer is not None:
+        if input_layer not in INPUT_LAYERS and not isinstance(input_layer, nn.Module) and input_layer is not None:
             raise ValueError("unknown input_layer: " + str(input_layer))
         unsupported = []
         # conformer_encoder.py:155-196: each rel-pos attention asserts its own positional encoding
@@ -154,32 +126,13 @@ class ConformerEncoder(AbsEncoder):
                 dropout_rate, normalize_before, concat_after, 0.0))
             layers[-1].layer_idx = lnum + 1
         self.encoders = nn.Sequential(*layers)
-        self.after_norm = _AfterNorm(output_size, eps=1e-12)
+        self.after_norm = AfterNorm(output_size, eps=1e-12)
         self.interctc_layer_idx = interctc_layer_idx
         if len(interctc_layer_idx) > 0:  # conformer_encoder.py:292-293
             assert 0 < min(interctc_layer_idx) and max(interctc_layer_idx) < num_blocks
         self.interctc_use_conditioning = interctc_use_conditioning
         self.conditioning_layer = None  # ESPnetASRModel creates it (a ConditioningLayer), as the reference does
         self._taps = TapState()
-
-    def output_size(self) -> int:
-        return self._output_size
-
-    def arena_groups(self, prefix=""):
-        g = []
-        for i in range(len(self.encoders)):
-            g += EncoderLayer.arena_groups(f"{prefix}encoders.{i}.")
-        return g
-
-    def bind(self, arena, prefix, cd, anchor):
-        self.embed.bind(arena, prefix + "embed.", cd)
-        self.embed._anchor = anchor
-        for i, layer in enumerate(self.encoders):
-            layer.bind(arena, f"{prefix}encoders.{i}.", cd)
-        self.after_norm.bind(arena, prefix + "after_norm.", cd)
-        if self.conditioning_layer is not None:
-            self.conditioning_layer.bind(arena, prefix + "conditioning_layer.", cd)
-        self._cd = cd
 
     def forward(self, xs_pad: torch.Tensor, ilens: torch.Tensor, prev_states=None, ctc=None,
                 seed: int = 0, interctc_targets=None) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
@@ -191,26 +144,13 @@ class ConformerEncoder(AbsEncoder):
         `interctc_targets` = (text (B, Lmax) padded with -1, text_lengths), for their losses,
         left in `self.interctc_losses` as [(layer, loss)] (espnet_model.py:242-286 computes them
         from the returned y; here the loss shares the tap's logits with the conditioning)."""
-        B, T, _ = xs_pad.shape
-        if T < 7:  # check_short_utt, subsampling.py:31-43
-            raise TooShortUttError(f"has {T} frames and is too short for subsampling "
-                                   f"(it needs more than 7 frames), return empty results", T, 7)
-        xs_pad = xs_pad.contiguous()
-        olens = torch.empty(B, dtype=torch.long, device=xs_pad.device)
-        lib.ea_subsample_lens(B, T, ilens.data_ptr(), olens.data_ptr(), ops.stream())
-        x = self.embed(xs_pad, seed)
         taps = self.interctc_layer_idx
-        if not taps:
-            multisequential_draw(len(self.encoders))
         # (with taps the reference loops over the layers itself, conformer_encoder.py:345: no
         # MultiSequential.forward, so no layer-drop draw from the host generator)
-        T2 = x.shape[1]
-        pos = self.embed.out[1].pos_emb(T2, x.device, self._cd, self.training, site_seed(seed, 0, 9))
+        x, olens = self.front(xs_pad, ilens, seed, layerdrop_draw=not taps)
+        pos = self.rel_pos_emb(x, seed)
         if not taps:
-            for layer in self.encoders:
-                x = layer(x, pos, olens, seed)
-            x = LayerNormFn.apply(x, self.after_norm)
-            return x, olens, None
+            return self.run_layers(x, pos, olens, seed), olens, None
         if ctc is None and self.interctc_use_conditioning:
             raise ValueError("interctc_use_conditioning needs the CTC head: encoder(..., ctc=model.ctc)")
         ys = ylens = None

@@ -15,20 +15,18 @@ from typing import Optional, Tuple
 import torch
 from torch import nn
 
-from ...layers.common import LayerNormFn, multisequential_draw, site_seed
 from ...layers.conformer import PositionwiseFeedForward, RelPositionMultiHeadedAttention
 from ...layers.ebranchformer import CONV_KERNELS, ConvolutionalGatingMLP, EBranchformerEncoderLayer
 from ...layers.subsampling import Conv2dSubsampling, RelPositionalEncoding
-from ... import hip_ops as ops
-from ..._lib import lib
-from .conformer_encoder import AbsEncoder, TooShortUttError, _AfterNorm
+from .abs_encoder import INPUT_LAYERS, AfterNorm, SubsamplingEncoder, resolve_rel_pos_type
 
-_INPUT_LAYERS = ("linear", "conv2d", "conv2d1", "conv2d2", "conv2d6", "conv2d8", "embed")
 # espnet/nets/pytorch_backend/nets_utils.py get_activation
 _ACTIVATIONS = ("hardtanh", "tanh", "relu", "selu", "swish")
 
 
-class EBranchformerEncoder(AbsEncoder):
+class EBranchformerEncoder(SubsamplingEncoder):
+    layer_class = EBranchformerEncoderLayer
+
     def __init__(
         self,
         input_size: int,
@@ -60,23 +58,15 @@ class EBranchformerEncoder(AbsEncoder):
         super().__init__()
         self._output_size = output_size
         # option resolution and validation as e_branchformer_encoder.py:215-352
-        if rel_pos_type == "legacy":
-            if pos_enc_layer_type == "rel_pos":
-                pos_enc_layer_type = "legacy_rel_pos"
-            if attention_layer_type == "rel_selfattn":
-                attention_layer_type = "legacy_rel_selfattn"
-        elif rel_pos_type == "latest":
-            assert attention_layer_type != "legacy_rel_selfattn"
-            assert pos_enc_layer_type != "legacy_rel_pos"
-        else:
-            raise ValueError("unknown rel_pos_type: " + rel_pos_type)
+        pos_enc_layer_type, attention_layer_type = resolve_rel_pos_type(
+            rel_pos_type, pos_enc_layer_type, attention_layer_type)
         if pos_enc_layer_type == "rel_pos":
             assert attention_layer_type == "rel_selfattn"
         elif pos_enc_layer_type == "legacy_rel_pos":
             assert attention_layer_type == "legacy_rel_selfattn"
         elif pos_enc_layer_type not in ("abs_pos", "scaled_abs_pos"):
             raise ValueError("unknown pos_enc_layer: " + pos_enc_layer_type)
-        if input_layer not in _INPUT_LAYERS and not isinstance(input_layer, nn.Module) and input_layer is not None:
+        if input_layer not in INPUT_LAYERS and not isinstance(input_layer, nn.Module) and input_layer is not None:
             raise ValueError("unknown input_layer: " + input_layer)
         if ffn_activation_type not in _ACTIVATIONS:  # get_activation's lookup
             raise KeyError(ffn_activation_type)
@@ -139,40 +129,11 @@ class EBranchformerEncoder(AbsEncoder):
                 dropout_rate, merge_conv_kernel))
             layers[-1].layer_idx = lnum + 1
         self.encoders = nn.Sequential(*layers)
-        self.after_norm = _AfterNorm(output_size, eps=1e-12)
-
-    def output_size(self) -> int:
-        return self._output_size
-
-    def arena_groups(self, prefix=""):
-        g = []
-        for i in range(len(self.encoders)):
-            g += EBranchformerEncoderLayer.arena_groups(f"{prefix}encoders.{i}.")
-        return g
-
-    def bind(self, arena, prefix, cd, anchor):
-        self.embed.bind(arena, prefix + "embed.", cd)
-        self.embed._anchor = anchor
-        for i, layer in enumerate(self.encoders):
-            layer.bind(arena, f"{prefix}encoders.{i}.", cd)
-        self.after_norm.bind(arena, prefix + "after_norm.", cd)
-        self._cd = cd
+        self.after_norm = AfterNorm(output_size, eps=1e-12)
 
     def forward(self, xs_pad: torch.Tensor, ilens: torch.Tensor, prev_states=None,
                 seed: int = 0) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
         """e_branchformer_encoder.py:384-430.  xs_pad (B,T,F) f32 on the GPU, ilens (B,) int64."""
-        B, T, _ = xs_pad.shape
-        if T < 7:  # check_short_utt, subsampling.py:31-43
-            raise TooShortUttError(f"has {T} frames and is too short for subsampling "
-                                   f"(it needs more than 7 frames), return empty results", T, 7)
-        xs_pad = xs_pad.contiguous()
-        olens = torch.empty(B, dtype=torch.long, device=xs_pad.device)
-        lib.ea_subsample_lens(B, T, ilens.data_ptr(), olens.data_ptr(), ops.stream())
-        x = self.embed(xs_pad, seed)
-        multisequential_draw(len(self.encoders))  # repeat() builds a MultiSequential (repeat.py:27)
-        T2 = x.shape[1]
-        pos = self.embed.out[1].pos_emb(T2, x.device, self._cd, self.training, site_seed(seed, 0, 9))
-        for layer in self.encoders:
-            x = layer(x, pos, olens, seed)
-        x = LayerNormFn.apply(x, self.after_norm)
-        return x, olens, None
+        x, olens = self.front(xs_pad, ilens, seed)  # (with repeat()'s MultiSequential draw, repeat.py:27)
+        pos = self.rel_pos_emb(x, seed)
+        return self.run_layers(x, pos, olens, seed), olens, None

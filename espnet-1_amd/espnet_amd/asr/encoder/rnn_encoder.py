@@ -36,7 +36,7 @@ import torch
 
 from ...layers.common import Bound, site_seed
 from ...lm.rnn_train import BiLSTMLayerFn, DropFn, LinearHead, LSTMLayer, OutLinearFn, TanhFn
-from .conformer_encoder import AbsEncoder
+from .abs_encoder import AbsEncoder
 
 _NOT_BUILT = "espnet_amd RNNEncoder: {} is not built"
 

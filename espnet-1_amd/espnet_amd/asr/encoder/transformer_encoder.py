@@ -16,17 +16,16 @@ from typing import List, Optional, Tuple
 import torch
 from torch import nn
 
-from ... import hip_ops as ops
-from ..._lib import lib
-from ...layers.common import LayerNormFn, multisequential_draw
 from ...layers.conformer import MultiHeadedAttention, PositionwiseFeedForward
 from ...layers.decoder import PositionalEncoding
 from ...layers.subsampling import Conv2dSubsampling
 from ...layers.transformer import TransformerEncoderLayer
-from .conformer_encoder import AbsEncoder, TooShortUttError, _AfterNorm
+from .abs_encoder import INPUT_LAYERS, AfterNorm, SubsamplingEncoder
 
 
-class TransformerEncoder(AbsEncoder):
+class TransformerEncoder(SubsamplingEncoder):
+    layer_class = TransformerEncoderLayer
+
     def __init__(
         self,
         input_size: int,
@@ -49,7 +48,7 @@ class TransformerEncoder(AbsEncoder):
     ):
         super().__init__()
         self._output_size = output_size
-        if input_layer not in ("linear", "conv2d", "conv2d1", "conv2d2", "conv2d6", "conv2d8", "embed", None):
+        if input_layer not in INPUT_LAYERS and input_layer is not None:
             raise ValueError("unknown input_layer: " + str(input_layer))
         if positionwise_layer_type not in ("linear", "conv1d", "conv1d-linear"):
             raise NotImplementedError("Support only linear or conv1d.")
@@ -80,41 +79,13 @@ class TransformerEncoder(AbsEncoder):
                 dropout_rate, normalize_before, concat_after))
             layers[-1].layer_idx = lnum + 1
         self.encoders = nn.Sequential(*layers)
-        self.after_norm = _AfterNorm(output_size, eps=1e-12)
+        self.after_norm = AfterNorm(output_size, eps=1e-12)
         self.interctc_layer_idx = interctc_layer_idx
         self.interctc_use_conditioning = interctc_use_conditioning
         self.conditioning_layer = None
 
-    def output_size(self) -> int:
-        return self._output_size
-
-    def arena_groups(self, prefix=""):
-        g = []
-        for i in range(len(self.encoders)):
-            g += TransformerEncoderLayer.arena_groups(f"{prefix}encoders.{i}.")
-        return g
-
-    def bind(self, arena, prefix, cd, anchor):
-        self.embed.bind(arena, prefix + "embed.", cd)
-        self.embed._anchor = anchor
-        for i, layer in enumerate(self.encoders):
-            layer.bind(arena, f"{prefix}encoders.{i}.", cd)
-        self.after_norm.bind(arena, prefix + "after_norm.", cd)
-        self._cd = cd
-
     def forward(self, xs_pad: torch.Tensor, ilens: torch.Tensor, prev_states=None, ctc=None,
                 seed: int = 0) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
         """transformer_encoder.py:184-232.  xs_pad (B,T,F) f32 on the GPU, ilens (B,) int64."""
-        B, T, _ = xs_pad.shape
-        if T < 7:  # check_short_utt, subsampling.py:31-43
-            raise TooShortUttError(f"has {T} frames and is too short for subsampling "
-                                   f"(it needs more than 7 frames), return empty results", T, 7)
-        xs_pad = xs_pad.contiguous()
-        olens = torch.empty(B, dtype=torch.long, device=xs_pad.device)
-        lib.ea_subsample_lens(B, T, ilens.data_ptr(), olens.data_ptr(), ops.stream())
-        x = self.embed(xs_pad, seed)
-        multisequential_draw(len(self.encoders))
-        for layer in self.encoders:
-            x = layer(x, olens, seed)
-        x = LayerNormFn.apply(x, self.after_norm)
-        return x, olens, None
+        x, olens = self.front(xs_pad, ilens, seed)
+        return self.run_layers(x, olens, seed), olens, None

@@ -18,9 +18,9 @@ import os
 import torch
 from torch import nn
 
-from .common import (ACT_SWISH, EPI_ACT, EPI_DACT, EPI_RESID, EPI_STORE, F32, Bound, attn_bwd, attn_dmask, dbd_layout,
-                     attn_fused_bwd, attn_fwd, empty, fused_attn_ok, lib, ln_bwd, ln_fwd, math, ops, rup,
-                     site_seed, dv_buf, drop_arg, site_dv, REL_LATEST, REL_LEGACY)
+from .common import (ACT_SWISH, EPI_RESID, F32, Bound, empty, lib, ln_bwd, ln_fwd, ops, site_seed, dv_buf, drop_arg,
+                     site_dv, REL_LATEST, REL_LEGACY)
+from .sublayers import ffn_bwd, ffn_fwd, rel_attn_bwd, rel_attn_fwd
 
 
 # ----------------------------------------------------------------------------- holders
@@ -145,45 +145,6 @@ class EncoderLayer(nn.Module):
         return ConformerBlockFn.apply(x, pos_emb, olens, self, seed, self.training)
 
 
-# ----------------------------------------------------------------------------- forward pieces
-def _ffn_fwd(L, b, x_in, pre, ln_name, p, seed_in, seed_out):
-    cd = b.cd
-    N, d = x_in.shape
-    Fh = L.feed_forward.w_1.out_features
-    xn, mu, rs = ln_fwd(x_in, b, ln_name, cd)
-    h = empty(N, Fh, dtype=cd, device=x_in.device)
-    a = empty(N, Fh, dtype=cd, device=x_in.device)
-    ops.linear(xn, b.w(pre + ".w_1.weight"), a,
-               epi=ops.make_epi(EPI_ACT, bias=b.f(pre + ".w_1.bias"), act=ACT_SWISH, aux=h,
-                                drop_p=p, seed=seed_in))
-    x_out = empty(N, d, device=x_in.device)
-    ops.linear(a, b.w(pre + ".w_2.weight"), x_out,
-               epi=ops.make_epi(EPI_RESID, bias=b.f(pre + ".w_2.bias"), resid=x_in,
-                                rscale=L.ff_scale, drop_p=p, seed=seed_out))
-    return x_out, (xn, mu, rs, h, a)
-
-
-def _ffn_bwd(L, b, dx, x_in, saved, pre, ln_name, p, seed_in, seed_out, dv_in=None, next_drop=None):
-    """dx: f32 (N,d) grad of the sub-block output; updated in place to grad of x_in.  dv_in: this
-    site's dv when already written; next_drop: the following site's (dv, scale, p, seed) for the
-    LayerNorm backward to write."""
-    cd = b.cd
-    xn, mu, rs, h, a = saved
-    N, d = dx.shape
-    dv = site_dv(dx, dv_in, b.g(pre + ".w_2.bias"), L.ff_scale, p, seed_out, cd)
-    with ops.wgrad(dv, a):
-        ops.linear_dw(dv, a, b.g(pre + ".w_2.weight"), accumulate=True)
-    dh = empty(*h.shape, dtype=cd, device=dx.device)
-    ops.linear_dx(dv, b.w(pre + ".w_2.weight"), dh,
-                  epi=ops.make_epi(EPI_DACT, act=ACT_SWISH, aux=h, drop_p=p, seed=seed_in))
-    with ops.wgrad(dh, xn):
-        ops.linear_dw(dh, xn, b.g(pre + ".w_1.weight"), accumulate=True,
-                      db=b.g(pre + ".w_1.bias"))
-    dxn = empty(N, d, dtype=cd, device=dx.device)
-    ops.linear_dx(dh, b.w(pre + ".w_1.weight"), dxn)
-    ln_bwd(dxn, x_in, b, ln_name, mu, rs, dx, accumulate=True, drop=next_drop)
-
-
 class ConformerBlockFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, pos, olens, L: EncoderLayer, seed, training):
@@ -193,71 +154,19 @@ class ConformerBlockFn(torch.autograd.Function):
         N = B * T
         dev = x.device
         H = L.self_attn.h
-        dk = d // H
-        P2 = 2 * T - 1
         p = L.dropout_rate if training else 0.0
         pa = L.self_attn.dropout_rate if training else 0.0
         li = L.layer_idx
         sd = lambda s: site_seed(seed, li, s)  # noqa: E731
+        ff = dict(act=ACT_SWISH, p_in=p, p_out=p, rscale=L.ff_scale)
         x0 = x.reshape(N, d)
         # ---- macaron FFN  (encoder_layer.py:115-123)
-        x1, s_ff1 = _ffn_fwd(L, b, x0, "feed_forward_macaron", "norm_ff_macaron", p, sd(1), sd(2))
+        x1, s_ff1 = ffn_fwd(b, x0, "feed_forward_macaron", "norm_ff_macaron", seed_in=sd(1), seed_out=sd(2), **ff)
         # ---- rel-pos MHSA (encoder_layer.py:126-149, attention.py:262-305)
         xn2, mu2, rs2 = ln_fwd(x1, b, "norm_mha", cd)
         A = "self_attn."
-        qkv = empty(N, 3 * d, dtype=cd, device=dev)
-        ops.linear(xn2, b.w(A + "linear_q.weight", A + "linear_k.weight", A + "linear_v.weight",
-                            shape=(3 * d, d)), qkv,
-                   epi=ops.make_epi(bias=b.f(A + "linear_q.bias", A + "linear_k.bias",
-                                             A + "linear_v.bias", shape=(3 * d,))))
         mode = L.self_attn.rel_mode
-        fused = fused_attn_ok(cd, dk, T, T)
-        if mode == REL_LEGACY and fused:
-            # the fused backward's d(q+v) GEMM runs over every physical column of the shifted band
-            # layout: `shift` zero rows in front of the table
-            shift = dbd_layout(T)[0]
-            pp_full = empty(shift + P2, d, dtype=cd, device=dev)
-            pp_full[:shift].zero_()
-            pp = pp_full[shift:]
-        else:
-            pp_full = None
-            pp = empty(P2, d, dtype=cd, device=dev)
-        if mode == REL_LEGACY:
-            # pos has T rows; the band is taken against Pext = [p; 0; p[:T-2]] (2T-1 rows)
-            assert pos.shape[0] == T
-            pT = empty(T, d, dtype=cd, device=dev)
-            ops.linear(pos, b.w(A + "linear_pos.weight"), pT)
-            lib.ea_legacy_pext(T, d, pT.data_ptr(), d, pp.data_ptr(), d, ops.dt(pp), ops.stream())
-        else:
-            ops.linear(pos, b.w(A + "linear_pos.weight"), pp)
-        scale = 1.0 / math.sqrt(dk)
-        if fused:
-            # one kernel: (q+u)k^T + rel_shift((q+v)p^T), mask, softmax, dropout, @v
-            O = empty(N, d, dtype=cd, device=dev)
-            lse = empty(B * H * T, device=dev)
-            dmask, ldm = attn_dmask(B * H * T, T, pa, dev)
-            lib.ea_attn_fused_fwd2_mode(B, H, T, T, dk, qkv.data_ptr(), 3 * d, qkv[:, d:].data_ptr(), 3 * d,
-                                        qkv[:, 2 * d:].data_ptr(), 3 * d, b.f(A + "pos_bias_u").data_ptr(),
-                                        b.f(A + "pos_bias_v").data_ptr(), pp.data_ptr(), d, olens.data_ptr(), 0,
-                                        scale, float(pa), sd(3), O.data_ptr(), d, lse.data_ptr(), ops.ptr(dmask), ldm,
-                                        mode, ops.stream())
-            ldT = 0
-            s_core = ("fused", lse, dmask, ldm, pp_full)
-        else:
-            qu = empty(N, d, dtype=cd, device=dev)
-            qv = empty(N, d, dtype=cd, device=dev)
-            lib.ea_add_pos_bias(N, H, dk, qkv.data_ptr(), 3 * d, b.f(A + "pos_bias_u").data_ptr(),
-                                b.f(A + "pos_bias_v").data_ptr(), qu.data_ptr(), qv.data_ptr(),
-                                ops.dt(qu), ops.stream())
-            ldbd = rup(P2, 8)
-            bd = empty(H * B * T * ldbd, device=dev)
-            ops.gemm(qv, pp, bd, M=T, N=P2, K=dk, a_kmajor=1, b_kmajor=1, lda=d, ldb=d, ldc=ldbd,
-                     batch=B, nh=H, sA=(T * d, dk), sB=(0, dk), sC=(T * ldbd, B * T * ldbd), splitk=False)
-            O, P, Pd, ldT = attn_fwd(qu, qkv[:, d:], qkv[:, 2 * d:], B=B, H=H, T1=T, T2=T, dk=dk,
-                                     ldq=d, ldk=3 * d, ldv=3 * d, klen=olens, causal=False, scale=scale,
-                                     p=pa, seed=sd(3), cd=cd, bd=bd, ldbd=ldbd, rel_mode=mode)
-            del bd
-            s_core = ("unfused", qu, qv, P, Pd)
+        O, s_core = rel_attn_fwd(b, A, xn2, pos, olens, B=B, T=T, H=H, rel_mode=mode, pa=pa, seed=sd(3))
         x2 = empty(N, d, device=dev)
         ops.linear(O, b.w(A + "linear_out.weight"), x2,
                    epi=ops.make_epi(EPI_RESID, bias=b.f(A + "linear_out.bias"), resid=x1,
@@ -311,11 +220,11 @@ class ConformerBlockFn(torch.autograd.Function):
                    epi=ops.make_epi(EPI_RESID, bias=b.f(C + "pointwise_conv2.bias"), resid=x2,
                                     drop_p=p, seed=sd(5)))
         # ---- FFN (encoder_layer.py:161-168) + norm_final (:170-171)
-        x4, s_ff2 = _ffn_fwd(L, b, x3, "feed_forward", "norm_ff", p, sd(6), sd(7))
+        x4, s_ff2 = ffn_fwd(b, x3, "feed_forward", "norm_ff", seed_in=sd(6), seed_out=sd(7), **ff)
         out, mu5, rs5 = ln_fwd(x4, b, "norm_final", F32)
         ctx.L = L
-        ctx.meta = (B, T, d, H, dk, p, pa, seed, scale, ldT, mode)
-        ctx.save = (x0, x1, x2, x3, x4, s_ff1, (xn2, mu2, rs2, qkv, pp, O, s_core),
+        ctx.meta = (B, T, d, H, p, pa, seed, mode)
+        ctx.save = (x0, x1, x2, x3, x4, s_ff1, (xn2, mu2, rs2, O, s_core),
                     (xn3, mu3, rs3, g2, glu, y, z, bn_mean, bn_rstd), s_ff2, (mu5, rs5), pos, olens)
         return out.view(B, T, d)
 
@@ -324,22 +233,22 @@ class ConformerBlockFn(torch.autograd.Function):
         L = ctx.L
         b = L._b
         cd = b.cd
-        B, T, d, H, dk, p, pa, seed, scale, ldT, mode = ctx.meta
+        B, T, d, H, p, pa, seed, mode = ctx.meta
         (x0, x1, x2, x3, x4, s_ff1, s_att, s_conv, s_ff2, (mu5, rs5), pos, olens) = ctx.save
         ctx.save = None
         li = L.layer_idx
         sd = lambda s: site_seed(seed, li, s)  # noqa: E731
+        ff = dict(act=ACT_SWISH, p_in=p, p_out=p, rscale=L.ff_scale)
         N = B * T
         dev = dout.device
-        P2 = 2 * T - 1
         dx = empty(N, d, device=dev)
         dv_ff2 = dv_buf(N, d, cd, dev)
         ln_bwd(dout.reshape(N, d).contiguous(), x4, b, "norm_final", mu5, rs5, dx, accumulate=False,
                drop=drop_arg(dv_ff2, L.ff_scale, p, sd(7), b.g("feed_forward.w_2.bias")))
         # ---- FFN
         dv_conv = dv_buf(N, d, cd, dev)
-        _ffn_bwd(L, b, dx, x3, s_ff2, "feed_forward", "norm_ff", p, sd(6), sd(7), dv_in=dv_ff2,
-                 next_drop=drop_arg(dv_conv, 1.0, p, sd(5), b.g("conv_module.pointwise_conv2.bias")))
+        ffn_bwd(b, dx, x3, s_ff2, "feed_forward", "norm_ff", seed_in=sd(6), seed_out=sd(7), dv_in=dv_ff2,
+                next_drop=drop_arg(dv_conv, 1.0, p, sd(5), b.g("conv_module.pointwise_conv2.bias")), **ff)
         # ---- conv module
         C = "conv_module."
         K = L.conv_module.kernel_size
@@ -381,98 +290,18 @@ class ConformerBlockFn(torch.autograd.Function):
                drop=drop_arg(dv_att, 1.0, p, sd(4), b.g("self_attn.linear_out.bias")))
         # ---- rel-pos MHSA
         A = "self_attn."
-        xn2, mu2, rs2, qkv, pp, O, s_core = s_att
+        xn2, mu2, rs2, O, s_core = s_att
         dv = site_dv(dx, dv_att, b.g(A + "linear_out.bias"), 1.0, p, sd(4), cd)
         with ops.wgrad(dv, O):
             ops.linear_dw(dv, O, b.g(A + "linear_out.weight"), accumulate=True)
         dO = empty(N, d, dtype=cd, device=dev)
         ops.linear_dx(dv, b.w(A + "linear_out.weight"), dO)
-        dqkv = empty(N, 3 * d, dtype=cd, device=dev)
-        ldbd, shift = rup(P2, 8), 0
-        if s_core[0] == "fused":
-            # dbd rows written in full, in the pipelined dQ pass's shifted layout (logical column r
-            # at r + shift); pos_bias_u / pos_bias_v gradients from per-block column sums of the dq
-            # terms.  Latest: dq includes the q+v path (dBD.p, in-kernel).  Legacy: the passes
-            # recompute the legacy scores and emit the band with the latest placement,
-            # ea_attn_legacy_band moves it onto the legacy rows, and d(q+v) is one batched GEMM
-            # over that band (the form of the unfused path below)
-            _, lse, dmask, ldm, pp_full = s_core
-            legacy = mode == REL_LEGACY
-            shift, ldbd = dbd_layout(T)
-            dbd = empty(H * B * T * ldbd, dtype=cd, device=dev)
-            qv = empty(N, d, dtype=cd, device=dev)  # q + v, for the linear_pos weight gradient
-            nqb = (T + 63) // 64
-            part = empty(2 * B * nqb * d, device=dev)
-            attn_fused_bwd(B=B, H=H, T1=T, T2=T, q=qkv, ldq=3 * d, k=qkv[:, d:], ldk=3 * d, v=qkv[:, 2 * d:],
-                           ldv=3 * d, bu=b.f(A + "pos_bias_u"), bv=b.f(A + "pos_bias_v"), pp=pp, ldp=d,
-                           klen=olens, causal=False, scale=scale, p=pa, seed=sd(3), O=O, ldo=d, lse=lse, dO=dO,
-                           lddo=d, dq=dqkv, lddq=3 * d, dk=dqkv[:, d:], lddk=3 * d, dv=dqkv[:, 2 * d:],
-                           lddv=3 * d, dbd=dbd, ldbd=ldbd, part=part, ldpart=d, qv_out=qv, ldqv=d, dmask=dmask,
-                           ldm=ldm, flags=2 if legacy else 1 | 2, rel_mode=mode)
-            ops.reduce_rows(part[:B * nqb * d], B * nqb, d, d, b.g(A + "pos_bias_u", shape=(d,)))
-            if legacy:
-                raw = dbd
-                dbd = empty(H * B * T * ldbd, dtype=cd, device=dev)
-                lib.ea_attn_legacy_band(H * B, T, raw.data_ptr(), dbd.data_ptr(), ldbd, ops.stream())
-                del raw
-                dqv = empty(N, d, dtype=cd, device=dev)
-                ops.gemm(dbd, pp_full, dqv, M=T, N=dk, K=shift + P2, a_kmajor=1, b_kmajor=0, lda=ldbd, ldb=d, ldc=d,
-                         batch=B, nh=H, sA=(T * ldbd, B * T * ldbd), sB=(0, dk), sC=(T * d, dk), splitk=False)
-                ops.colsum(dqv, b.g(A + "pos_bias_v", shape=(d,)))
-                lib.ea_add_2d(N, d, dqv.data_ptr(), ops.dt(dqv), d, dqkv.data_ptr(), ops.dt(dqkv), 3 * d, 1.0,
-                              ops.stream())
-            else:
-                ops.reduce_rows(part[B * nqb * d:], B * nqb, d, d, b.g(A + "pos_bias_v", shape=(d,)))
-        else:
-            _, qu, qv, P, Pd = s_core
-            dbd = empty(H * B * T * ldbd, dtype=cd, device=dev)
-            attn_bwd(dO, qu, qkv[:, d:], qkv[:, 2 * d:], P, Pd, ldT, B=B, H=H, T1=T, T2=T, dk=dk,
-                     ldq=d, ldk=3 * d, ldv=3 * d, scale=scale, p=pa, seed=sd(3), cd=cd,
-                     dq=dqkv, lddq=3 * d, dk_=dqkv[:, d:], lddk=3 * d, dv=dqkv[:, 2 * d:], lddv=3 * d,
-                     dbd=dbd, ldbd=ldbd, rel_mode=mode)
-            # q_u = q + u: du = sum dq_u ; q_v = q + v path: dq_v = dBD . p_h, dv_bias = sum dq_v
-            dqv = empty(N, d, dtype=cd, device=dev)
-            ops.gemm(dbd, pp, dqv, M=T, N=dk, K=P2, a_kmajor=1, b_kmajor=0, lda=ldbd, ldb=d, ldc=d,
-                     batch=B, nh=H, sA=(T * ldbd, B * T * ldbd), sB=(0, dk), sC=(T * d, dk), splitk=False)
-            # not deferred: dqkv[:, :d] receives dqv in place right below
-            ops.colsum(dqkv[:, :d], b.g(A + "pos_bias_u", shape=(d,)), defer=False)
-            ops.colsum(dqv, b.g(A + "pos_bias_v", shape=(d,)))
-            lib.ea_add_2d(N, d, dqv.data_ptr(), ops.dt(dqv), d, dqkv.data_ptr(), ops.dt(dqkv), 3 * d, 1.0,
-                          ops.stream())
-        qkv_w = b.w(A + "linear_q.weight", A + "linear_k.weight", A + "linear_v.weight", shape=(3 * d, d))
-        # linear_pos: dp[h] = sum_b dBD[h][b]^T qv[b, :, h]  (K = B*T), dWpos = dp^T pos; with the
-        # shifted layout the GEMM runs over every physical column and rows [shift, shift + P2) of
-        # its output are dp
-
-        def dpp_wgrad(after=None):
-            with ops.wgrad(dbd, qv, pos, after=after, launches=True):
-                Mp = P2 + shift if shift else P2
-                dpp_full = empty(Mp, d, dtype=cd, device=dev)
-                ops.gemm(dbd, qv, dpp_full, M=Mp, N=dk, K=B * T, a_kmajor=0, b_kmajor=0, lda=ldbd, ldb=d, ldc=d,
-                         batch=1, nh=H, sA=(0, B * T * ldbd), sB=(0, dk), sC=(0, dk))
-                dpp = dpp_full[shift:]
-                if mode == REL_LEGACY:  # dp[k] = dPext[k] + dPext[T+1+k] over pos's T rows
-                    dpp = empty(T, d, dtype=cd, device=dev)
-                    lib.ea_legacy_pext_fold(T, d, dpp_full[shift:].data_ptr(), d, dpp.data_ptr(), d, ops.dt(dpp),
-                                            ops.stream())
-                ops.linear_dw(dpp, pos, b.g(A + "linear_pos.weight"), accumulate=True)
-
-        fork = ops.fork_event()
-        if fork is None:
-            dpp_wgrad()
-        with ops.wgrad(dqkv, xn2):
-            ops.linear_dw(dqkv, xn2, b.g(A + "linear_q.weight", A + "linear_k.weight", A + "linear_v.weight",
-                                          shape=(3 * d, d)), accumulate=True,
-                          db=b.g(A + "linear_q.bias", A + "linear_k.bias", A + "linear_v.bias", shape=(3 * d,)))
-        dxn2 = empty(N, d, dtype=cd, device=dev)
-        ops.linear_dx(dqkv, qkv_w, dxn2)
-        if fork is not None:  # the side GEMM issued after the main chain's next kernel (fork_event)
-            dpp_wgrad(after=fork)
-        del dbd
+        dxn2 = rel_attn_bwd(b, A, dO, xn2, O, s_core, pos, olens, B=B, T=T, H=H, rel_mode=mode, pa=pa, seed=sd(3))
         dv_ff1 = dv_buf(N, d, cd, dev)
         ln_bwd(dxn2, x1, b, "norm_mha", mu2, rs2, dx, accumulate=True,
                drop=drop_arg(dv_ff1, L.ff_scale, p, sd(2), b.g("feed_forward_macaron.w_2.bias")))
         # ---- macaron FFN
-        _ffn_bwd(L, b, dx, x0, s_ff1, "feed_forward_macaron", "norm_ff_macaron", p, sd(1), sd(2), dv_in=dv_ff1)
+        ffn_bwd(b, dx, x0, s_ff1, "feed_forward_macaron", "norm_ff_macaron", seed_in=sd(1), seed_out=sd(2),
+                dv_in=dv_ff1, **ff)
         ops.grad_ready(b)
         return dx.view(B, T, d), None, None, None, None, None

@@ -25,9 +25,10 @@ import ctypes
 import torch
 from torch import nn
 
-from .common import (EPI_RESID, EPI_STORE, F32, Bound, attn_bwd, attn_dmask, attn_fused_bwd, attn_fwd, dbd_layout,
-                     drop_arg, dv_buf, empty, fused_attn_ok, lib, ln_bwd, ln_fwd, math, ops, rup, site_dv, site_seed)
-from .conformer import LayerNorm, _ffn_bwd, _ffn_fwd
+from .common import (ACT_SWISH, EPI_RESID, EPI_STORE, F32, REL_LATEST, Bound, drop_arg, dv_buf, empty, lib, ln_bwd,
+                     ln_fwd, ops, site_dv, site_seed)
+from .conformer import LayerNorm
+from .sublayers import ffn_bwd, ffn_fwd, rel_attn_bwd, rel_attn_fwd
 
 CONV_KERNELS = (3, 5, 7, 15, 31)  # the depthwise kernels' compiled widths
 
@@ -104,118 +105,6 @@ class EBranchformerEncoderLayer(nn.Module):
         return EBranchformerBlockFn.apply(x, pos_emb, olens, self, seed, self.training)
 
 
-# ----------------------------------------------------------------------------- attention branch
-def _attn_fwd(L, b, xn, pos, olens, B, T, pa, seed3):
-    """Rel-pos MHSA core of layers/conformer.py on the `attn.` parameters (attention.py:262-305):
-    xn (N, d) cd -> O (N, d) cd, before linear_out."""
-    cd = b.cd
-    N, d = xn.shape
-    dev = xn.device
-    H = L.attn.h
-    dk = d // H
-    P2 = 2 * T - 1
-    A = "attn."
-    qkv = empty(N, 3 * d, dtype=cd, device=dev)
-    ops.linear(xn, b.w(A + "linear_q.weight", A + "linear_k.weight", A + "linear_v.weight", shape=(3 * d, d)), qkv,
-               epi=ops.make_epi(bias=b.f(A + "linear_q.bias", A + "linear_k.bias", A + "linear_v.bias",
-                                         shape=(3 * d,))))
-    pp = empty(P2, d, dtype=cd, device=dev)
-    ops.linear(pos, b.w(A + "linear_pos.weight"), pp)
-    scale = 1.0 / math.sqrt(dk)
-    if fused_attn_ok(cd, dk, T, T):
-        O = empty(N, d, dtype=cd, device=dev)
-        lse = empty(B * H * T, device=dev)
-        dmask, ldm = attn_dmask(B * H * T, T, pa, dev)
-        lib.ea_attn_fused_fwd2(B, H, T, T, dk, qkv.data_ptr(), 3 * d, qkv[:, d:].data_ptr(), 3 * d,
-                               qkv[:, 2 * d:].data_ptr(), 3 * d, b.f(A + "pos_bias_u").data_ptr(),
-                               b.f(A + "pos_bias_v").data_ptr(), pp.data_ptr(), d, olens.data_ptr(), 0,
-                               scale, float(pa), seed3, O.data_ptr(), d, lse.data_ptr(), ops.ptr(dmask), ldm,
-                               ops.stream())
-        ldT = 0
-        s_core = ("fused", lse, dmask, ldm)
-    else:
-        qu = empty(N, d, dtype=cd, device=dev)
-        qv = empty(N, d, dtype=cd, device=dev)
-        lib.ea_add_pos_bias(N, H, dk, qkv.data_ptr(), 3 * d, b.f(A + "pos_bias_u").data_ptr(),
-                            b.f(A + "pos_bias_v").data_ptr(), qu.data_ptr(), qv.data_ptr(), ops.dt(qu), ops.stream())
-        ldbd = rup(P2, 8)
-        bd = empty(H * B * T * ldbd, device=dev)
-        ops.gemm(qv, pp, bd, M=T, N=P2, K=dk, a_kmajor=1, b_kmajor=1, lda=d, ldb=d, ldc=ldbd,
-                 batch=B, nh=H, sA=(T * d, dk), sB=(0, dk), sC=(T * ldbd, B * T * ldbd), splitk=False)
-        O, P, Pd, ldT = attn_fwd(qu, qkv[:, d:], qkv[:, 2 * d:], B=B, H=H, T1=T, T2=T, dk=dk,
-                                 ldq=d, ldk=3 * d, ldv=3 * d, klen=olens, causal=False, scale=scale,
-                                 p=pa, seed=seed3, cd=cd, bd=bd, ldbd=ldbd)
-        del bd
-        s_core = ("unfused", qu, qv, P, Pd)
-    return O, (qkv, pp, s_core, scale, ldT)
-
-
-def _attn_bwd(L, b, dO, xn, O, saved, pos, olens, B, T, pa, seed3):
-    """Backward of _attn_fwd: parameter gradients of linear_q/k/v, linear_pos, pos_bias_u/v into
-    the arena; returns dxn (N, d) cd."""
-    cd = b.cd
-    N, d = xn.shape
-    dev = dO.device
-    H = L.attn.h
-    dk = d // H
-    P2 = 2 * T - 1
-    A = "attn."
-    qkv, pp, s_core, scale, ldT = saved
-    dqkv = empty(N, 3 * d, dtype=cd, device=dev)
-    ldbd, shift = rup(P2, 8), 0
-    if s_core[0] == "fused":
-        _, lse, dmask, ldm = s_core
-        shift, ldbd = dbd_layout(T)
-        dbd = empty(H * B * T * ldbd, dtype=cd, device=dev)
-        qv = empty(N, d, dtype=cd, device=dev)  # q + v, for the linear_pos weight gradient
-        nqb = (T + 63) // 64
-        part = empty(2 * B * nqb * d, device=dev)
-        attn_fused_bwd(B=B, H=H, T1=T, T2=T, q=qkv, ldq=3 * d, k=qkv[:, d:], ldk=3 * d, v=qkv[:, 2 * d:],
-                       ldv=3 * d, bu=b.f(A + "pos_bias_u"), bv=b.f(A + "pos_bias_v"), pp=pp, ldp=d,
-                       klen=olens, causal=False, scale=scale, p=pa, seed=seed3, O=O, ldo=d, lse=lse, dO=dO,
-                       lddo=d, dq=dqkv, lddq=3 * d, dk=dqkv[:, d:], lddk=3 * d, dv=dqkv[:, 2 * d:],
-                       lddv=3 * d, dbd=dbd, ldbd=ldbd, part=part, ldpart=d, qv_out=qv, ldqv=d, dmask=dmask,
-                       ldm=ldm, flags=1 | 2)
-        ops.reduce_rows(part[:B * nqb * d], B * nqb, d, d, b.g(A + "pos_bias_u", shape=(d,)))
-        ops.reduce_rows(part[B * nqb * d:], B * nqb, d, d, b.g(A + "pos_bias_v", shape=(d,)))
-    else:
-        _, qu, qv, P, Pd = s_core
-        dbd = empty(H * B * T * ldbd, dtype=cd, device=dev)
-        attn_bwd(dO, qu, qkv[:, d:], qkv[:, 2 * d:], P, Pd, ldT, B=B, H=H, T1=T, T2=T, dk=dk,
-                 ldq=d, ldk=3 * d, ldv=3 * d, scale=scale, p=pa, seed=seed3, cd=cd,
-                 dq=dqkv, lddq=3 * d, dk_=dqkv[:, d:], lddk=3 * d, dv=dqkv[:, 2 * d:], lddv=3 * d,
-                 dbd=dbd, ldbd=ldbd)
-        dqv = empty(N, d, dtype=cd, device=dev)
-        ops.gemm(dbd, pp, dqv, M=T, N=dk, K=P2, a_kmajor=1, b_kmajor=0, lda=ldbd, ldb=d, ldc=d,
-                 batch=B, nh=H, sA=(T * ldbd, B * T * ldbd), sB=(0, dk), sC=(T * d, dk), splitk=False)
-        # not deferred: dqkv[:, :d] receives dqv in place right below
-        ops.colsum(dqkv[:, :d], b.g(A + "pos_bias_u", shape=(d,)), defer=False)
-        ops.colsum(dqv, b.g(A + "pos_bias_v", shape=(d,)))
-        lib.ea_add_2d(N, d, dqv.data_ptr(), ops.dt(dqv), d, dqkv.data_ptr(), ops.dt(dqkv), 3 * d, 1.0, ops.stream())
-    qkv_w = b.w(A + "linear_q.weight", A + "linear_k.weight", A + "linear_v.weight", shape=(3 * d, d))
-
-    def dpp_wgrad(after=None):
-        with ops.wgrad(dbd, qv, pos, after=after, launches=True):
-            Mp = P2 + shift if shift else P2
-            dpp_full = empty(Mp, d, dtype=cd, device=dev)
-            ops.gemm(dbd, qv, dpp_full, M=Mp, N=dk, K=B * T, a_kmajor=0, b_kmajor=0, lda=ldbd, ldb=d, ldc=d,
-                     batch=1, nh=H, sA=(0, B * T * ldbd), sB=(0, dk), sC=(0, dk))
-            ops.linear_dw(dpp_full[shift:], pos, b.g(A + "linear_pos.weight"), accumulate=True)
-
-    fork = ops.fork_event()
-    if fork is None:
-        dpp_wgrad()
-    with ops.wgrad(dqkv, xn):
-        ops.linear_dw(dqkv, xn, b.g(A + "linear_q.weight", A + "linear_k.weight", A + "linear_v.weight",
-                                    shape=(3 * d, d)), accumulate=True,
-                      db=b.g(A + "linear_q.bias", A + "linear_k.bias", A + "linear_v.bias", shape=(3 * d,)))
-    dxn = empty(N, d, dtype=cd, device=dev)
-    ops.linear_dx(dqkv, qkv_w, dxn)
-    if fork is not None:  # the side GEMM issued after the main chain's next kernel (fork_event)
-        dpp_wgrad(after=fork)
-    return dxn
-
-
 def _long(v=0):
     return ctypes.c_long(v)
 
@@ -234,16 +123,18 @@ class EBranchformerBlockFn(torch.autograd.Function):
         li = L.layer_idx
         sd = lambda s: site_seed(seed, li, s)  # noqa: E731
         macaron = L.feed_forward_macaron is not None
+        ff = dict(act=ACT_SWISH, p_in=p, p_out=p, rscale=L.ff_scale)
         x0 = x.reshape(N, d)
         # ---- macaron FFN (e_branchformer_encoder.py:126-129)
         if macaron:
-            x1, s_ff1 = _ffn_fwd(L, b, x0, "feed_forward_macaron", "norm_ff_macaron", p, sd(1), sd(2))
+            x1, s_ff1 = ffn_fwd(b, x0, "feed_forward_macaron", "norm_ff_macaron", seed_in=sd(1), seed_out=sd(2), **ff)
         else:
             x1, s_ff1 = x0, None
         xc = empty(N, 2 * d, dtype=cd, device=dev)  # x_concat = [x1 | x2]
         # ---- branch 1: rel-pos MHSA, no residual (:136-146)
         xna, mua, rsa = ln_fwd(x1, b, "norm_mha", cd)
-        O, s_core = _attn_fwd(L, b, xna, pos, olens, B, T, pa, sd(3))
+        O, s_core = rel_attn_fwd(b, "attn.", xna, pos, olens, B=B, T=T, H=L.attn.h, rel_mode=REL_LATEST, pa=pa,
+                                 seed=sd(3))
         ops.linear(O, b.w("attn.linear_out.weight"), xc[:, :d],
                    epi=ops.make_epi(EPI_STORE, bias=b.f("attn.linear_out.bias"), drop_p=p, seed=sd(4)))
         # ---- branch 2: convolutional gating MLP (:149-157, cgmlp.py:110-118)
@@ -273,7 +164,7 @@ class EBranchformerBlockFn(torch.autograd.Function):
         ops.linear(m, b.w("merge_proj.weight"), x2,
                    epi=ops.make_epi(EPI_RESID, bias=b.f("merge_proj.bias"), resid=x1, drop_p=p, seed=sd(7)))
         # ---- FFN (:166-170) + norm_final (:172)
-        x3, s_ff2 = _ffn_fwd(L, b, x2, "feed_forward", "norm_ff", p, sd(8), sd(9))
+        x3, s_ff2 = ffn_fwd(b, x2, "feed_forward", "norm_ff", seed_in=sd(8), seed_out=sd(9), **ff)
         out, muf, rsf = ln_fwd(x3, b, "norm_final", F32)
         ctx.L = L
         ctx.meta = (B, T, d, p, pa, pg, seed)
@@ -292,6 +183,7 @@ class EBranchformerBlockFn(torch.autograd.Function):
         li = L.layer_idx
         sd = lambda s: site_seed(seed, li, s)  # noqa: E731
         macaron = L.feed_forward_macaron is not None
+        ff = dict(act=ACT_SWISH, p_in=p, p_out=p, rscale=L.ff_scale)
         N = B * T
         dev = dout.device
         dx = empty(N, d, device=dev)
@@ -300,8 +192,8 @@ class EBranchformerBlockFn(torch.autograd.Function):
                drop=drop_arg(dv_ff2, L.ff_scale, p, sd(9), b.g("feed_forward.w_2.bias")))
         # ---- FFN
         dv_mg = dv_buf(N, d, cd, dev)
-        _ffn_bwd(L, b, dx, x2, s_ff2, "feed_forward", "norm_ff", p, sd(8), sd(9), dv_in=dv_ff2,
-                 next_drop=drop_arg(dv_mg, 1.0, p, sd(7), b.g("merge_proj.bias")))
+        ffn_bwd(b, dx, x2, s_ff2, "feed_forward", "norm_ff", seed_in=sd(8), seed_out=sd(9), dv_in=dv_ff2,
+                next_drop=drop_arg(dv_mg, 1.0, p, sd(7), b.g("merge_proj.bias")), **ff)
         # ---- merge: dm = dv . W_merge, dxc = (dm + dwconv^T(dm)) * the two branch dropout masks
         dv = site_dv(dx, dv_mg, b.g("merge_proj.bias"), 1.0, p, sd(7), cd)
         with ops.wgrad(dv, m):
@@ -358,12 +250,14 @@ class EBranchformerBlockFn(torch.autograd.Function):
                           db=b.g("attn.linear_out.bias"))
         dO = empty(N, d, dtype=cd, device=dev)
         ops.linear_dx(dv1, b.w("attn.linear_out.weight"), dO)
-        dxna = _attn_bwd(L, b, dO, xna, O, s_core, pos, olens, B, T, pa, sd(3))
+        dxna = rel_attn_bwd(b, "attn.", dO, xna, O, s_core, pos, olens, B=B, T=T, H=L.attn.h, rel_mode=REL_LATEST,
+                            pa=pa, seed=sd(3))
         if macaron:
             dv_ff1 = dv_buf(N, d, cd, dev)
             ln_bwd(dxna, x1, b, "norm_mha", mua, rsa, dx, accumulate=True,
                    drop=drop_arg(dv_ff1, L.ff_scale, p, sd(2), b.g("feed_forward_macaron.w_2.bias")))
-            _ffn_bwd(L, b, dx, x0, s_ff1, "feed_forward_macaron", "norm_ff_macaron", p, sd(1), sd(2), dv_in=dv_ff1)
+            ffn_bwd(b, dx, x0, s_ff1, "feed_forward_macaron", "norm_ff_macaron", seed_in=sd(1), seed_out=sd(2),
+                    dv_in=dv_ff1, **ff)
         else:
             ln_bwd(dxna, x1, b, "norm_mha", mua, rsa, dx, accumulate=True)
         ops.grad_ready(b)

@@ -17,10 +17,10 @@ import math
 import torch
 from torch import nn
 
-from .common import (ACT_RELU, EPI_ACT, EPI_DACT, EPI_RESID, Bound, empty, ln_bwd, ln_fwd, ops, site_dv,
-                     site_seed)
+from .common import ACT_RELU, EPI_RESID, Bound, empty, ln_bwd, ln_fwd, ops, site_dv, site_seed
 from .conformer import LayerNorm
 from .decoder import _mha_bwd, _mha_fwd
+from .sublayers import ffn_bwd, ffn_fwd
 
 
 class TransformerEncoderLayer(nn.Module):
@@ -85,19 +85,11 @@ class TransformerBlockFn(torch.autograd.Function):
                    epi=ops.make_epi(EPI_RESID, bias=b.f("self_attn.linear_out.bias"), resid=x0, drop_p=p,
                                     seed=sd(2)))
         # ---- feed-forward (ReLU)
-        xn2, mu2, rs2 = ln_fwd(x1, b, "norm2", cd)
-        Fh = L.feed_forward.w_1.out_features
-        h = empty(N, Fh, dtype=cd, device=dev)
-        a = empty(N, Fh, dtype=cd, device=dev)
-        ops.linear(xn2, b.w("feed_forward.w_1.weight"), a,
-                   epi=ops.make_epi(EPI_ACT, bias=b.f("feed_forward.w_1.bias"), act=ACT_RELU, aux=h, drop_p=p_ff,
-                                    seed=sd(3)))
-        x2 = empty(N, d, device=dev)
-        ops.linear(a, b.w("feed_forward.w_2.weight"), x2,
-                   epi=ops.make_epi(EPI_RESID, bias=b.f("feed_forward.w_2.bias"), resid=x1, drop_p=p, seed=sd(4)))
+        x2, s_ff = ffn_fwd(b, x1, "feed_forward", "norm2", act=ACT_RELU, p_in=p_ff, p_out=p, rscale=1.0,
+                           seed_in=sd(3), seed_out=sd(4))
         ctx.L = L
         ctx.meta = (B, T, d, H, dk, p, pa, p_ff, seed, scale)
-        ctx.save = (x0, x1, (xn1, mu1, rs1, qkv, O, st), (xn2, mu2, rs2, h, a), olens)
+        ctx.save = (x0, x1, (xn1, mu1, rs1, qkv, O, st), s_ff, olens)
         return x2.view(B, T, d)
 
     @staticmethod
@@ -113,19 +105,8 @@ class TransformerBlockFn(torch.autograd.Function):
         dev = dout.device
         dx = dout.reshape(N, d).contiguous().clone()
         # ---- feed-forward
-        xn2, mu2, rs2, h, a = s_ff
-        dv = site_dv(dx, None, b.g("feed_forward.w_2.bias"), 1.0, p, sd(4), cd)
-        with ops.wgrad(dv, a):
-            ops.linear_dw(dv, a, b.g("feed_forward.w_2.weight"), accumulate=True)
-        dh = empty(*h.shape, dtype=cd, device=dev)
-        ops.linear_dx(dv, b.w("feed_forward.w_2.weight"), dh,
-                      epi=ops.make_epi(EPI_DACT, act=ACT_RELU, aux=h, drop_p=p_ff, seed=sd(3)))
-        with ops.wgrad(dh, xn2):
-            ops.linear_dw(dh, xn2, b.g("feed_forward.w_1.weight"), accumulate=True,
-                          db=b.g("feed_forward.w_1.bias"))
-        dxn = empty(N, d, dtype=cd, device=dev)
-        ops.linear_dx(dh, b.w("feed_forward.w_1.weight"), dxn)
-        ln_bwd(dxn, x1, b, "norm2", mu2, rs2, dx, accumulate=True)
+        ffn_bwd(b, dx, x1, s_ff, "feed_forward", "norm2", act=ACT_RELU, p_in=p_ff, p_out=p, rscale=1.0,
+                seed_in=sd(3), seed_out=sd(4))
         # ---- self-attention
         xn1, mu1, rs1, qkv, O, st = s_att
         dv = site_dv(dx, None, b.g("self_attn.linear_out.bias"), 1.0, p, sd(2), cd)

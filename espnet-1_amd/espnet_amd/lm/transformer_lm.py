@@ -28,7 +28,7 @@ from ..arena import ParamArena
 from ..layers.common import LayerNormFn
 from ..layers.conformer import MultiHeadedAttention, PositionwiseFeedForward
 from ..layers.transformer import TransformerEncoderLayer
-from ..asr.encoder.conformer_encoder import _AfterNorm
+from ..asr.encoder.abs_encoder import AfterNorm
 
 
 class _Encoder(nn.Module):
@@ -47,7 +47,7 @@ class _Encoder(nn.Module):
             layers[-1].layer_idx = 100 + i
             layers[-1].causal = True
         self.encoders = nn.Sequential(*layers)
-        self.after_norm = _AfterNorm(attention_dim, eps=1e-12)
+        self.after_norm = AfterNorm(attention_dim, eps=1e-12)
 
 
 class TransformerLM(nn.Module):

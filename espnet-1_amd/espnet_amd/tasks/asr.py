@@ -23,7 +23,8 @@ from ..asr.abs_modules import AbsFrontend, AbsNormalize, AbsSpecAug
 from ..asr.ctc import CTC
 from ..asr.decoder.rnn_decoder import RNNDecoder
 from ..asr.decoder.transformer_decoder import AbsDecoder, TransformerDecoder
-from ..asr.encoder.conformer_encoder import AbsEncoder, ConformerEncoder
+from ..asr.encoder.abs_encoder import AbsEncoder
+from ..asr.encoder.conformer_encoder import ConformerEncoder
 from ..asr.encoder.e_branchformer_encoder import EBranchformerEncoder
 from ..asr.encoder.rnn_encoder import RNNEncoder
 from ..asr.encoder.transformer_encoder import TransformerEncoder

@@ -211,7 +211,7 @@ def test_fused_amp_step_matches_the_unfused_amp_step(monkeypatch):
     allowed 6e-2 per tensor from the fp32 reference (test_legacy_bf16_amp_close); the same bound is
     asked between them."""
     from espnet_amd._lib import REL_LEGACY, lib
-    from espnet_amd.layers import conformer
+    from espnet_amd.layers import sublayers
     calls = []
     real = lib.ea_attn_fused_bwd2_mode
     monkeypatch.setattr(lib, "ea_attn_fused_bwd2_mode", lambda *a: (calls.append(a[-2]), real(*a))[1])
@@ -219,7 +219,7 @@ def test_fused_amp_step_matches_the_unfused_amp_step(monkeypatch):
     assert calls.count(REL_LEGACY) == len(m.encoder.encoders)  # (the decoder's calls are latest)
     fused = {k: p.grad.double().cpu() for k, p in m.named_parameters()}
     n = len(calls)
-    monkeypatch.setattr(conformer, "fused_attn_ok", lambda *a: False)
+    monkeypatch.setattr(sublayers, "fused_attn_ok", lambda *a: False)
     _, _, m2, loss2, _, _ = run("legacy_dk64", amp=True)
     assert REL_LEGACY not in calls[n:]
     np.testing.assert_allclose(loss.item(), loss2.item(), rtol=2e-2)
