@@ -28,6 +28,7 @@ from ..asr.encoder.conformer_encoder import ConformerEncoder
 from ..asr.encoder.e_branchformer_encoder import EBranchformerEncoder
 from ..asr.encoder.rnn_encoder import RNNEncoder
 from ..asr.encoder.transformer_encoder import TransformerEncoder
+from ..asr.encoder.vgg_rnn_encoder import VGGRNNEncoder
 from ..asr.espnet_model import AbsESPnetModel, ESPnetASRModel, UtteranceMVN
 from ..asr.frontend.default import DefaultFrontend, GlobalMVN
 from ..asr.specaug import SpecAug
@@ -44,7 +45,8 @@ normalize_choices = ClassChoices("normalize", dict(global_mvn=GlobalMVN, utteran
                                  type_check=AbsNormalize, default="utterance_mvn", optional=True)
 model_choices = ClassChoices("model", dict(espnet=ESPnetASRModel), type_check=AbsESPnetModel, default="espnet")
 encoder_choices = ClassChoices("encoder", dict(conformer=ConformerEncoder, transformer=TransformerEncoder,
-                                               e_branchformer=EBranchformerEncoder, rnn=RNNEncoder),
+                                               e_branchformer=EBranchformerEncoder, rnn=RNNEncoder,
+                                               vgg_rnn=VGGRNNEncoder),
                                type_check=AbsEncoder, default="rnn")
 decoder_choices = ClassChoices("decoder", dict(transformer=TransformerDecoder, rnn=RNNDecoder), type_check=AbsDecoder,
                                default=None, optional=True)

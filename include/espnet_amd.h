@@ -1022,6 +1022,66 @@ int ea_attloc_bwd(int mdtype, int B, int T, int E, int A, int C, int F, const vo
                   float* dhs, long lddhs, long sdhs, float* ddec, long ldddec, float* daprev, long ldda,
                   float* part, long ldpart, float* ws, long ws_floats, void* stream);
 
+/* ---------------------------------------------------------------- VGG2L (encoder: vgg_rnn) */
+
+/* The four Conv2d(3x3, stride 1, pad 1) + ReLU layers and the two max_pool2d(2, 2, ceil_mode) of
+ * VGG2L (espnet/nets/pytorch_backend/rnn/encoders.py:178-237) over channel-last activations
+ * (B, H, W, C), H = time, W = feature; dtype EA_F32 (exact f32 MFMA) or EA_BF16 (f32 accumulate).
+ *
+ * ea_vgg_conv3x3 is an implicit GEMM (no im2col): rows = the B*H*W pixels, N = cout, K = 9*cin in
+ * (tap, channel) order, w (cout, 9, cin) in `dtype`; taps outside the image contribute zeros.  With
+ * flip the weight's tap index is 8 - tap: over w = (Ci, 9, Co), the forward weight transposed, the
+ * same launch is the layer's input gradient.  cin, cout in {64, 128}.
+ *   src  EA_VGG_SRC_PLAIN : x (B, H, W, cin) in `dtype`.
+ *        EA_VGG_SRC_POOLED: the rows are the full-resolution gradient of a pooled layer, never
+ *          materialised: element (b, h, w, c) is dp[i] when the decision byte dec[i] names window
+ *          position 2*(h&1) + (w&1) as the winner and that position's ReLU bit is set, else 0, with
+ *          i = b*ps_b + (h/2)*ps_h + (w/2)*ps_w + c*ps_c.  dp is f32.
+ *   epi  EA_VGG_EPI_NONE: out = acc (+ bias when given);  EA_VGG_EPI_RELU: out = relu(acc + bias);
+ *        EA_VGG_EPI_MASK: out = aux > 0 ? acc : 0, aux (B, H, W, cout) in `dtype` (the ReLU mask of
+ *          the layer below, taken from its stored output);
+ *        EA_VGG_EPI_POOL: bias, ReLU and the 2x2 pool in registers, on the f32 value: out and
+ *          dec_out at b*po_b + h2*po_h + w2*po_w + n*po_c hold the window's maximum and its
+ *          decision byte: bits 0-1 the argmax 2*dt + df (first in the scan dt outer, df inner under
+ *          strict >, over the ReLU outputs, so an all-nonpositive window names position 0), bit
+ *          2 + pos = (pre-activation of position pos > 0).  A window at an odd extent's edge has one
+ *          row or column.
+ *   out is (B, H, W, cout) except under EA_VGG_EPI_POOL, in out_dtype.
+ *
+ * ea_vgg_wgrad: part[s][co][tap][ci] = sum over pixel range s of dY[p][co] * x[p + tap][ci], x
+ * (B, H, W, cin), dY (B, H, W, cout) plain or through the decisions as above; nsplit from
+ * ea_vgg_wgrad_splits (ranges of whole 32-pixel chunks, at most 128); the caller sums the ranges
+ * in order (ea_reduce_partials).  (cout, cin) in {(64, 64), (128, 64), (128, 128)}.
+ * ea_vgg_pool_dbias: part[blk][c] = the block's share of sum_i dp[i] over pooled elements whose
+ * winner's ReLU bit is set (c < cout; only B, H, W, cout and ps_* of the geometry are read).  The
+ * caller chooses nparts in 1 .. 65535: block blk takes pooled pixels [blk, blk + 1) * ceil(Q / nparts)
+ * (zeros past Q) with 256 / cout threads per channel, which cout in {64, 128} divides.
+ *
+ * conv1_1 (cin = 1): ea_vgg_conv1_fwd y (B, H, W, 64) = relu(conv(x (B, H, W) f32, w (64, 9) f32)
+ * + bias) in `dtype`; ea_vgg_conv1_wgrad part[blk][c*9 + t] = sum_p dy[p][c] x_t(p) and
+ * part[blk][576 + c] = sum_p dy[p][c] over block blk's pixels (640 floats per block).
+ * No atomics: equal inputs give bit-equal outputs. */
+enum { EA_VGG_SRC_PLAIN = 0, EA_VGG_SRC_POOLED = 1 };
+enum { EA_VGG_EPI_NONE = 0, EA_VGG_EPI_RELU = 1, EA_VGG_EPI_MASK = 2, EA_VGG_EPI_POOL = 3 };
+/* geo: EA_VGG_NGEO host ints, strides: EA_VGG_NSTRIDE host longs (element strides b, h, w, c of the
+ * pooled source ps_* and of the pooled output po_*), both read before the call returns */
+enum { EA_VGG_B = 0, EA_VGG_H = 1, EA_VGG_W = 2, EA_VGG_CIN = 3, EA_VGG_COUT = 4, EA_VGG_SRC = 5, EA_VGG_EPI = 6,
+       EA_VGG_FLIP = 7, EA_VGG_OUT_DTYPE = 8, EA_VGG_NGEO = 9 };
+enum { EA_VGG_PS_B = 0, EA_VGG_PS_H = 1, EA_VGG_PS_W = 2, EA_VGG_PS_C = 3, EA_VGG_PO_B = 4, EA_VGG_PO_H = 5,
+       EA_VGG_PO_W = 6, EA_VGG_PO_C = 7, EA_VGG_NSTRIDE = 8 };
+int ea_vgg_conv3x3(const int* geo, const long* strides, int dtype, const void* x, const float* dp,
+                   const unsigned char* dec, const void* w, const float* bias, const void* aux, void* out,
+                   unsigned char* dec_out, void* stream);
+int ea_vgg_wgrad_splits(const int* geo, int* nsplit);
+int ea_vgg_wgrad(const int* geo, const long* strides, int dtype, const void* x, const void* dy, const float* dp,
+                 const unsigned char* dec, float* part, int nsplit, void* stream);
+int ea_vgg_pool_dbias(const int* geo, const long* strides, const float* dp, const unsigned char* dec, float* part, int nparts,
+                      void* stream);
+int ea_vgg_conv1_fwd(int B, int H, int W, const float* x, const float* w, const float* bias, void* y, int dtype,
+                     void* stream);
+int ea_vgg_conv1_wgrad(int B, int H, int W, const float* x, const void* dy, int dtype, float* part, int nparts,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif
