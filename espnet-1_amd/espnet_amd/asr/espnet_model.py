@@ -23,6 +23,7 @@ from ..layers.interctc import InterCTCMixFn
 from ..layers.losses import CombineFn, LabelSmoothingLossFn
 from .ctc import CTC
 from .error_calculator import ErrorCalculator
+from .joint_network import RNNTLoss
 from .abs_modules import AbsNormalize
 
 
@@ -102,8 +103,17 @@ class ESPnetASRModel(AbsESPnetModel):
         super().__init__()
         if preencoder is not None or postencoder is not None:
             raise NotImplementedError("preencoder/postencoder are outside the HIP hot path (SURVEY.md §2a)")
-        if joint_network is not None or lang_token_id != -1:
-            raise NotImplementedError("transducer / lang token are not on the path")
+        if lang_token_id != -1:
+            raise NotImplementedError("lang token is not on the path")
+        if joint_network is not None and (report_cer or report_wer):
+            raise NotImplementedError(f"report_cer={report_cer} / report_wer={report_wer} with a transducer decoder: "
+                                      "ErrorCalculatorTransducer needs the transducer beam search, which is not built")
+        if joint_network is not None and ctc_weight == 1.0:
+            raise NotImplementedError("ctc_weight=1.0 with a transducer decoder: the model drops its decoder at "
+                                      "ctc_weight 1.0 and the transducer loss needs it")
+        if joint_network is not None and ignore_id >= 0:
+            raise NotImplementedError(f"ignore_id={ignore_id} with a transducer decoder: the transducer targets are "
+                                      "read off a text padded with a negative id")
         taps = list(getattr(encoder, "interctc_layer_idx", None) or [])
         if taps and aux_ctc:
             raise NotImplementedError("aux_ctc with intermediate CTC: a tap's loss shares its logits with the "
@@ -135,15 +145,20 @@ class ESPnetASRModel(AbsESPnetModel):
         if self.encoder.interctc_use_conditioning:
             from .encoder.conformer_encoder import ConditioningLayer
             self.encoder.conditioning_layer = ConditioningLayer(vocab_size, self.encoder.output_size())
-        self.use_transducer_decoder = False
+        self.use_transducer_decoder = joint_network is not None  # espnet_model.py:110-134
         self.error_calculator = None
+        if self.use_transducer_decoder:
+            self.joint_network = joint_network
+            self.criterion_transducer = RNNTLoss(blank=self.blank_id, fastemit_lambda=0.0)
+            self.error_calculator_trans = None
         if ctc_weight < 1.0:
             assert decoder is not None, "decoder should not be None when attention is used"
         else:
             decoder = None
             logging.warning("Set decoder to none as ctc_weight==1.0")
         self.decoder = decoder
-        self.criterion_att = LabelSmoothingLoss(vocab_size, ignore_id, lsm_weight, length_normalized_loss)
+        if not self.use_transducer_decoder:
+            self.criterion_att = LabelSmoothingLoss(vocab_size, ignore_id, lsm_weight, length_normalized_loss)
         if report_cer or report_wer:  # espnet_model.py:164-167 (used in eval mode only)
             self.error_calculator = ErrorCalculator(token_list, sym_space, sym_blank, report_cer, report_wer)
         self.ctc = None if ctc_weight == 0.0 else ctc
@@ -180,6 +195,8 @@ class ESPnetASRModel(AbsESPnetModel):
         g = self.encoder.arena_groups("encoder.")
         if self.decoder is not None:
             g += self.decoder.arena_groups("decoder.")
+        if self.use_transducer_decoder:
+            g += self.joint_network.arena_groups("joint_network.")
         return g
 
     def prepare(self, device="cuda", amp: bool = False, seed: int = 0):
@@ -208,6 +225,8 @@ class ESPnetASRModel(AbsESPnetModel):
         self.encoder.bind(self.arena, "encoder.", cd, self._anchor)
         if self.decoder is not None:
             self.decoder.bind(self.arena, "decoder.", cd)
+        if self.use_transducer_decoder:
+            self.joint_network.bind(self.arena, "joint_network.", cd)
         if self.ctc is not None:
             self.ctc.bind(self.arena, "ctc.", cd)
         self.seed = seed
@@ -300,7 +319,13 @@ class ESPnetASRModel(AbsESPnetModel):
                 stats[f"cer_interctc_layer{layer_idx}"] = cer_ic
         else:
             losses = None
-        if self.ctc_weight != 1.0:
+        if self.use_transducer_decoder:  # espnet_model.py:288-310
+            loss_transducer = self._calc_transducer_loss(encoder_out, encoder_out_lens, text, text_lengths,
+                                                         seed=site_seed(seed, 600, 2))
+            stats["loss_transducer"] = loss_transducer.detach()
+            stats["cer_transducer"] = None
+            stats["wer_transducer"] = None
+        elif self.ctc_weight != 1.0:
             loss_att, acc_att = self._calc_att_loss(encoder_out, encoder_out_lens, text, text_lengths,
                                                     seed=site_seed(seed, 600, 1))
             stats["loss_att"] = loss_att.detach()
@@ -319,7 +344,13 @@ class ESPnetASRModel(AbsESPnetModel):
             # loss_ctc = (1-w)*loss_ctc + w*mean(tap losses), espnet_model.py:281-286 (the taps'
             # lattices ran on the auxiliary stream too; stats["loss_ctc"] is the unmixed loss)
             loss_ctc = InterCTCMixFn.apply(float(self.interctc_weight), loss_ctc, *[l for _, l in losses])
-        if self.ctc_weight == 0.0:
+        if self.use_transducer_decoder:
+            if loss_ctc is not None:
+                ops.take_aux_fork()
+                loss = CombineFn.apply(loss_ctc, loss_transducer, float(self.ctc_weight), 1.0)
+            else:
+                loss = loss_transducer
+        elif self.ctc_weight == 0.0:
             loss = loss_att
         elif self.ctc_weight == 1.0:
             loss = loss_ctc
@@ -380,6 +411,18 @@ class ESPnetASRModel(AbsESPnetModel):
         out = torch.empty(B, L1, dtype=torch.long, device=lg.device)
         lib.ea_argmax_rows(B * L1, V, lg.data_ptr(), V, out.data_ptr(), ops.stream())
         return out.cpu()
+
+    def _calc_transducer_loss(self, encoder_out, encoder_out_lens, labels, label_lens, seed=0):
+        """espnet_model.py:577-623 (training path: cer / wer None).  get_transducer_task_io without its
+        host loop: the text is already -1-padded and its lengths are on the device, so decoder_in =
+        [blank, labels], target = labels (padding -> blank), t_len and u_len are elementwise."""
+        B = labels.shape[0]
+        target = labels.masked_fill(labels < 0, self.blank_id)
+        decoder_in = torch.cat([target.new_full((B, 1), self.blank_id), target], dim=1)
+        decoder_out = self.decoder(decoder_in, seed=seed)
+        return self.criterion_transducer(self.joint_network, encoder_out.float(), decoder_out,
+                                         target.to(torch.int32).contiguous(), encoder_out_lens.to(torch.int32),
+                                         label_lens.to(torch.int32))
 
     def _calc_att_loss(self, encoder_out, encoder_out_lens, ys_pad, ys_pad_lens, seed=0):
         """espnet_model.py:518-553 (training path: cer/wer None)."""

@@ -28,6 +28,12 @@ def _encode(model, speech, speech_lengths):
     return enc, olens
 
 
+def _attention_decoder_only(model):
+    if getattr(model, "use_transducer_decoder", False):
+        raise NotImplementedError("decoder: transducer: transducer decoding (greedy / beam search over the joint "
+                                  "network) is not built; ctc_greedy serves a model trained with ctc_weight > 0")
+
+
 def _collapse(ids, blank=0):
     out, prev = [], None
     for t in ids:
@@ -56,6 +62,7 @@ def ctc_greedy(model, speech: torch.Tensor, speech_lengths: torch.Tensor) -> Lis
 @torch.no_grad()
 def attention_greedy(model, speech: torch.Tensor, speech_lengths: torch.Tensor, maxlenratio: float = 0.0,
                      minlenratio: float = 0.0) -> List[Tuple[List[int], float]]:
+    _attention_decoder_only(model)
     if minlenratio != 0.0:
         raise NotImplementedError("minlenratio > 0 (beam_search.py retry loop) is not implemented")
     was = model.training
@@ -101,6 +108,7 @@ def attention_beam_search(model, speech: torch.Tensor, speech_lengths: torch.Ten
     scorer (ctc_weight, pre-beam "full") and LengthBonus (length_bonus): per utterance the
     n-best list of Hypothesis records (yseq with <sos>/<eos>, score, per-scorer scores)."""
     from .beam_search import BatchBeamSearch, BeamSearch, CTCPrefixScorer, LengthBonus
+    _attention_decoder_only(model)
     if batch:  # espnet/nets/batch_beam_search.py under its own name (the same batched search)
         BeamSearch = BatchBeamSearch  # noqa: N806
     was = model.training

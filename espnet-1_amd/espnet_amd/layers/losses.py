@@ -184,21 +184,24 @@ class LabelSmoothingLossFn(torch.autograd.Function):
 
 
 class CombineFn(torch.autograd.Function):
-    """loss = w*a + (1-w)*b  (espnet_model.py:325)."""
+    """loss = w*a + wb*b, wb = 1 - w unless given  (espnet_model.py:325: w*ctc + (1-w)*att; :301 with
+    wb = 1: ctc_weight*ctc + loss_transducer)."""
 
     @staticmethod
-    def forward(ctx, a, b, w):
+    def forward(ctx, a, b, w, wb=None):
+        wb = 1.0 - w if wb is None else wb
         out = empty((), device=a.device)
-        lib.ea_axpby_scalar(a.data_ptr(), w, b.data_ptr(), 1.0 - w, out.data_ptr(), ops.stream())
-        ctx.w = w
+        lib.ea_axpby_scalar(a.data_ptr(), w, b.data_ptr(), wb, out.data_ptr(), ops.stream())
+        ctx.w = (w, wb)
         return out
 
     @staticmethod
     def backward(ctx, g):
         g = _g(g)
+        w, wb = ctx.w
         ga = empty((), device=g.device)
         gb = empty((), device=g.device)
-        lib.ea_axpby_scalar(g.data_ptr(), ctx.w, 0, 0.0, ga.data_ptr(), ops.stream())
-        lib.ea_axpby_scalar(g.data_ptr(), 1.0 - ctx.w, 0, 0.0, gb.data_ptr(), ops.stream())
+        lib.ea_axpby_scalar(g.data_ptr(), w, 0, 0.0, ga.data_ptr(), ops.stream())
+        lib.ea_axpby_scalar(g.data_ptr(), wb, 0, 0.0, gb.data_ptr(), ops.stream())
         ops.mark_aux_fork()  # the CTC head's backward forks from here (CTCFn.backward)
-        return ga, gb, None
+        return ga, gb, None, None

@@ -22,6 +22,7 @@ import numpy as np
 from ..asr.abs_modules import AbsFrontend, AbsNormalize, AbsSpecAug
 from ..asr.ctc import CTC
 from ..asr.decoder.rnn_decoder import RNNDecoder
+from ..asr.decoder.transducer_decoder import TransducerDecoder
 from ..asr.decoder.transformer_decoder import AbsDecoder, TransformerDecoder
 from ..asr.encoder.abs_encoder import AbsEncoder
 from ..asr.encoder.conformer_encoder import ConformerEncoder
@@ -31,6 +32,7 @@ from ..asr.encoder.transformer_encoder import TransformerEncoder
 from ..asr.encoder.vgg_rnn_encoder import VGGRNNEncoder
 from ..asr.espnet_model import AbsESPnetModel, ESPnetASRModel, UtteranceMVN
 from ..asr.frontend.default import DefaultFrontend, GlobalMVN
+from ..asr.joint_network import JointNetwork
 from ..asr.specaug import SpecAug
 from ..train.class_choices import ClassChoices
 from ..train.collate_fn import CommonCollateFn
@@ -48,7 +50,8 @@ encoder_choices = ClassChoices("encoder", dict(conformer=ConformerEncoder, trans
                                                e_branchformer=EBranchformerEncoder, rnn=RNNEncoder,
                                                vgg_rnn=VGGRNNEncoder),
                                type_check=AbsEncoder, default="rnn")
-decoder_choices = ClassChoices("decoder", dict(transformer=TransformerDecoder, rnn=RNNDecoder), type_check=AbsDecoder,
+decoder_choices = ClassChoices("decoder", dict(transformer=TransformerDecoder, rnn=RNNDecoder,
+                                               transducer=TransducerDecoder), type_check=AbsDecoder,
                                default=None, optional=True)
 # the registries the reference also exposes, empty here (nothing on the training path uses them)
 preencoder_choices = ClassChoices("preencoder", dict(), default=None, optional=True)
@@ -68,6 +71,11 @@ class _IntTextPreprocessor:
 
     def __call__(self, uid, data):
         text = data.get("text")
+        if isinstance(text, np.ndarray) and self.token_list is not None and text.size and \
+                not (0 <= int(text.min()) and int(text.max()) < len(self.token_list)):
+            # the loss kernels index the vocabulary by these ids unchecked (a transducer label >= V would
+            # give an infinite loss with no error): refuse the utterance here, on the host
+            raise ValueError(f"{uid}: token id outside [0, {len(self.token_list)}) in text")
         if text is None or isinstance(text, np.ndarray):
             return data
         if self.token_type != "char" or self.token_list is None:
@@ -187,12 +195,16 @@ def build_model(args) -> ESPnetASRModel:
     enc_cls = encoder_choices.get_class(_get(args, "encoder", "conformer"))
     encoder = enc_cls(input_size=input_size, **(_get(args, "encoder_conf") or {}))
     dec_cls = decoder_choices.get_class(_get(args, "decoder"))
-    decoder = None
-    if dec_cls is not None:
+    decoder = joint_network = None
+    if _get(args, "decoder") == "transducer":  # asr.py:547-559
+        decoder = dec_cls(vocab_size, embed_pad=0, **(_get(args, "decoder_conf") or {}))
+        joint_network = JointNetwork(vocab_size, encoder.output_size(), decoder.dunits,
+                                     **(_get(args, "joint_net_conf") or {}))
+    elif dec_cls is not None:
         decoder = dec_cls(vocab_size=vocab_size, encoder_output_size=encoder.output_size(),
                           **(_get(args, "decoder_conf") or {}))
     ctc = CTC(odim=vocab_size, encoder_output_size=encoder.output_size(), **(_get(args, "ctc_conf") or {}))
     model_cls = model_choices.get_class(_get(args, "model", "espnet") or "espnet")
     return model_cls(vocab_size=vocab_size, frontend=frontend, specaug=specaug, normalize=normalize,
                      preencoder=None, encoder=encoder, postencoder=None, decoder=decoder, ctc=ctc,
-                     joint_network=None, token_list=token_list, **(_get(args, "model_conf") or {}))
+                     joint_network=joint_network, token_list=token_list, **(_get(args, "model_conf") or {}))

@@ -1082,6 +1082,51 @@ int ea_vgg_conv1_fwd(int B, int H, int W, const float* x, const float* w, const 
 int ea_vgg_conv1_wgrad(int B, int H, int W, const float* x, const void* dy, int dtype, float* part, int nparts,
                        void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * RNN-Transducer: the joint network fused with the RNN-T loss (csrc/transducer.hip).  Replaces
+ * JointNetwork.forward's tanh + lin_out (espnet2/asr_transducer/joint_network.py:57-59) and
+ * warprnnt_pytorch.RNNTLoss(blank=0, fastemit_lambda=0) (espnet2/asr/espnet_model.py:115-123,
+ * 606-615), whose (B, T, U1, V) logits are never stored.
+ *
+ * N = B*T*U1 lattice nodes, U1 = Umax + 1, node row r = (b*T + t)*U1 + u.  E = lin_enc(enc) (B, T, J)
+ * and D = lin_dec(dec) (B, U1, J) f32 contiguous, 16-B aligned; W (V, J) rows of ldw elements and the
+ * rounded h in `dtype` (EA_F32 / EA_BF16), 16-B aligned rows; bias (V) f32; y (B, U1 - 1), t_len and
+ * u_len (B) int32 in device memory; blank = 0.  A node is live when t < t_len[b] and u <= u_len[b].
+ * Precondition, not checked on the device: 0 <= y[b,u] < V for u < u_len[b] (a label outside the
+ * vocabulary matches no column, its lp_label is -inf and the loss inf; the data path checks ids on the host).
+ * J % 8 == 0 and J <= EA_RNNT_MAX_JOINT (the h tile of a workgroup stays in LDS for the whole kernel);
+ * U1 <= EA_RNNT_MAX_U1 (two lattice diagonals in LDS).  V and J need not be tile multiples.
+ *
+ * ea_rnnt_joint_lse: per live node lse = logsumexp_v(logit), lp_blank = logit_0 - lse, lp_label =
+ *   logit_{y[b,u]} - lse (0 at u = u_len[b]), logit = tanh(E[b,t] + D[b,u]) . W^T + bias with h rounded
+ *   to `dtype` and f32 accumulation; each (B, T, U1) f32.  Padding nodes are not written.
+ * ea_rnnt_lattice: alpha, beta (B, T, U1) in log space over the live nodes, ll[b] = beta(0, 0), all f64
+ *   (they grow like |ll|; in f32 their rounding alone would cost gamma a relative 2^-24 |ll|), then in f32 gamma = exp(alpha + beta - ll), k_blank = exp(alpha + lp_blank + beta(t+1, u) - ll) (at the
+ *   terminal node exp(alpha + lp_blank - ll)), k_label = exp(alpha + lp_label + beta(t, u+1) - ll)
+ *   for u < u_len, zeros on padding nodes, and loss[0] = -(1/B) sum_b ll[b].
+ * ea_rnnt_joint_dlogits: for the node rows of (b, t) rows bt0 .. bt0 + nbt - 1, recomputing the logits,
+ *   dlogits[r - bt0*U1][v] = (gloss[0] / B) * (gamma_r exp(logit - lse_r) - [v = 0] k_blank_r
+ *   - [v = y] k_label_r) in `dtype`, rows of V <= ldl <= V rounded up to 128 elements (columns V .. ldl - 1 and the rows of
+ *   padding nodes are zeros), and h (nbt*U1, J) in `dtype`, the rounded joint activations of the chunk.
+ * ea_rnnt_joint_dact: dh (nbt*U1, J) f32, the chunk's gradient of h, becomes dpre = dh (1 - h^2) in
+ *   place (h recomputed in f32); dE[b,t,:] = sum_u dpre for the chunk's (b, t); dD[b,u,:] = (the chunk
+ *   holds t = 0 of b) or += (otherwise) the sum over the chunk's t of b in increasing order, so chunks
+ *   given in increasing bt0 leave every dD a fixed-order sum and need no cleared buffer.
+ * No atomics: equal inputs give bit-equal outputs. */
+enum { EA_RNNT_MAX_JOINT = 640, EA_RNNT_MAX_U1 = 4096 };
+int ea_rnnt_joint_lse(int dtype, int B, int T, int U1, int V, int J, const float* E, const float* D, const void* W,
+                      long ldw, const float* bias, const int* y, const int* t_len, const int* u_len, float* lse,
+                      float* lp_blank, float* lp_label, void* stream);
+int ea_rnnt_lattice(int B, int T, int U1, const float* lp_blank, const float* lp_label, const int* t_len,
+                    const int* u_len, double* alpha, double* beta, double* ll, float* gamma, float* k_blank,
+                    float* k_label, float* loss, void* stream);
+int ea_rnnt_joint_dlogits(int dtype, int B, int T, int U1, int V, int J, const float* E, const float* D, const void* W,
+                          long ldw, const float* bias, const int* y, const int* t_len, const int* u_len,
+                          const float* lse, const float* gamma, const float* k_blank, const float* k_label,
+                          const float* gloss, long bt0, long nbt, void* dlogits, long ldl, void* h, void* stream);
+int ea_rnnt_joint_dact(int B, int T, int U1, int J, const float* E, const float* D, const int* t_len, const int* u_len,
+                       long bt0, long nbt, float* dh, float* dE, float* dD, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
