@@ -9,7 +9,11 @@
   Each utterance is encoded alone, as Speech2Text does (a padded batch would let the
   conformer's depthwise convolution see padding frames).
 
-Both run the model in eval mode (dropout off, BatchNorm running statistics).
+* ``transducer_decode`` — espnet2/asr/transducer/beam_search_transducer.py for a `decoder: transducer`
+  model: the greedy search and the default beam search over the joint-step kernels
+  (csrc/transducer_step.hip); greedy over several utterances runs batched.
+
+All run the model in eval mode (dropout off, BatchNorm running statistics).
 """
 from __future__ import annotations
 
@@ -95,6 +99,74 @@ def attention_greedy(model, speech: torch.Tensor, speech_lengths: torch.Tensor, 
                     break
             res.append((yseq[1:-1], score))
         return res
+    finally:
+        model.train(was)
+
+
+def _batched_greedy(model, encs: List[torch.Tensor]) -> List[Tuple[List[int], float]]:
+    """BeamSearchTransducer.greedy_search over up to EA_RNNT_STEP_MAX_ROWS utterances at once: iteration t
+    is one joint step with row i at frame min(t, T_i - 1) of its utterance, one decoder step of every row
+    on the token it would emit and one project_dec; a row that emits takes the new state and D row, the
+    others keep theirs (torch.where by mask).  Nothing synchronises with the host until the one copy of the
+    (B, Tmax) tokens and scores at the end."""
+    dec, jn = model.decoder, model.joint_network
+    B, dev = len(encs), encs[0].device
+    lens = [int(e.shape[0]) for e in encs]
+    Tmax = max(lens)
+    E = torch.zeros(B, Tmax, jn.joint_space_size, device=dev)
+    for i, e in enumerate(encs):
+        E[i, :lens[i]] = jn.project_enc(e.float())
+    E = E.view(B * Tmax, -1)
+    tl = torch.tensor(lens, dtype=torch.int32).to(dev)
+    t_idx = torch.arange(Tmax, dtype=torch.int32, device=dev)[:, None]
+    frames = (torch.arange(B, dtype=torch.int32, device=dev) * Tmax)[None, :] + torch.minimum(t_idx, tl[None, :] - 1)
+    live = t_idx < tl[None, :]  # (Tmax, B): a row with t >= T_i is dead
+    dec.set_device(dev)
+    dec_out, state = dec.step(torch.full((B,), dec.blank_id, dtype=torch.long, device=dev), dec.init_state(B))
+    D = jn.project_dec(dec_out)
+    out = torch.zeros(2, Tmax, B, dtype=torch.int32, device=dev)  # token (0: none), the score's bits
+    for t in range(Tmax):
+        r = jn.step(E, frames[t], D, 1)
+        tok, val = r.top_id[:, 0], r.top_value[:, 0]
+        emit = (val > r.lp_blank) & live[t]  # blank, at index 0, wins ties (torch.max: the first maximum)
+        new_out, new_state = dec.step(tok.long(), state)
+        new_D = jn.project_dec(new_out)
+        state = tuple(torch.where(emit[None, :, None], a, b) for a, b in zip(new_state, state))
+        D = torch.where(emit[:, None], new_D, D)
+        out[0, t] = torch.where(emit, tok, 0)
+        out[1, t] = torch.where(emit, val, 0.0).view(torch.int32)
+    out = out.cpu()
+    toks, vals = out[0].t().tolist(), out[1].view(torch.float32).t().tolist()
+    return [([y for y in toks[i] if y], float(sum(v for y, v in zip(toks[i], vals[i]) if y))) for i in range(B)]
+
+
+@torch.no_grad()
+def transducer_decode(model, speech: torch.Tensor, speech_lengths: torch.Tensor, beam_size: int = 1, nbest: int = 1,
+                      score_norm: bool = True) -> List[List[Tuple[List[int], float]]]:
+    """Decoding of a `decoder: transducer` model (espnet2/bin/asr_inference.py with a transducer decoder:
+    BeamSearchTransducer, search_type "default"): per utterance the n-best list of (yseq without the leading
+    blank, score).  Each utterance is encoded alone.  beam_size <= 1 is the greedy search; more than one
+    utterance then runs batched, EA_RNNT_STEP_MAX_ROWS at a time (_batched_greedy)."""
+    from .._lib import RNNT_STEP_MAX_ROWS
+    from .transducer.beam_search_transducer import BeamSearchTransducer
+    if not getattr(model, "use_transducer_decoder", False):
+        raise ValueError("transducer_decode: the model has no transducer decoder (attention_greedy / "
+                         "attention_beam_search / ctc_greedy serve the others)")
+    search = BeamSearchTransducer(model.decoder, model.joint_network, beam_size, score_norm=score_norm, nbest=nbest)
+    was = model.training
+    model.eval()
+    try:
+        encs = []
+        for b in range(speech.shape[0]):
+            le = int(speech_lengths[b])
+            enc, olens = _encode(model, speech[b:b + 1, :le], speech_lengths[b:b + 1])
+            encs.append(enc[0, :int(olens[0])])
+        if beam_size <= 1 and len(encs) > 1:
+            res = []
+            for i in range(0, len(encs), RNNT_STEP_MAX_ROWS):
+                res += [[r] for r in _batched_greedy(model, encs[i:i + RNNT_STEP_MAX_ROWS])]
+            return res
+        return [[(h.yseq[1:], float(h.score)) for h in search(enc)] for enc in encs]
     finally:
         model.train(was)
 

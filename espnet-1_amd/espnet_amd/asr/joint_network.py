@@ -16,14 +16,49 @@ ONE autograd node, RNNTJointLossFn, over csrc/transducer.hip: the logits are nev
 Four f32 per node live from forward to backward (lse and the three coefficients).  Under amp h, W_out and
 the stored dlogits are bf16; E, D and every sum are f32, the lattice recurrences f64.  The chunk count depends on the
 shapes only and nothing synchronises with the host, so a training step stays capturable as one graph.
+
+Decoding: E = project_enc(enc_out) once per utterance, D = project_dec(dec_out) per new
+label sequence, and step(E, frame, D, k) over csrc/transducer_step.hip for n <= 64 hypotheses at once:
+    ea_rnnt_step_logits   tanh + lin_out with the vocabulary split over the grid; the (n, V) logits and a
+                          (max, sum exp) pair per vocabulary slice and row
+    ea_rnnt_step_select   lse, lp_blank, the top k non-blank log-probabilities and ids per row
 """
 from __future__ import annotations
 
 import torch
 
+from typing import NamedTuple, Optional
+
 from .. import hip_ops as ops
-from .._lib import RNNT_MAX_JOINT, RNNT_MAX_U1, dt, lib  # noqa: F401  (bound from the header's enums)
+from .._lib import (RNNT_MAX_JOINT, RNNT_MAX_U1, RNNT_STEP_MAX_K, RNNT_STEP_MAX_ROWS,  # noqa: F401
+                    RNNT_STEP_SW, dt, lib)  # (bound from the header's enums)
 from ..layers.common import Bound, rup
+
+
+class JointStep(NamedTuple):
+    """JointNetwork.step's outputs, views of one device buffer (`packed`)."""
+    lse: torch.Tensor
+    lp_blank: torch.Tensor
+    top_value: torch.Tensor
+    top_id: torch.Tensor
+    logp: Optional[torch.Tensor]
+    packed: torch.Tensor
+
+    def host(self):
+        """One device-to-host copy -> (lp_blank (n), top values (n, k), top ids (n, k)) as lists."""
+        (n, k), p = self.top_id.shape, self.packed.cpu()
+        return (p[n:2 * n].tolist(), p[2 * n:2 * n + n * k].view(n, k).tolist(),
+                p[2 * n + n * k:].view(torch.int32).view(n, k).tolist())
+
+
+def check_step(n: int, k: int, V: int):
+    """The joint-step kernels' limits (include/espnet_amd.h), refused by name."""
+    if not 1 <= n <= RNNT_STEP_MAX_ROWS:
+        raise ValueError(f"JointNetwork.step: n={n} rows; the joint-step kernel takes 1 .. {RNNT_STEP_MAX_ROWS} "
+                         "(EA_RNNT_STEP_MAX_ROWS)")
+    if not 1 <= k <= min(RNNT_STEP_MAX_K, V - 1):
+        raise ValueError(f"JointNetwork.step: k={k} with vocabulary {V}; the selection takes 1 .. "
+                         f"min({RNNT_STEP_MAX_K}, V - 1) (EA_RNNT_STEP_MAX_K)")
 
 
 def f32c(t: torch.Tensor) -> torch.Tensor:
@@ -194,6 +229,54 @@ class JointNetwork(torch.nn.Module):
         D = JointLinearFn.apply(dec_out.reshape(B * U1, -1), self._lin("lin_dec"))
         return E.view(B, T, J), D.view(B, U1, J)
 
+    # ------------------------------------------------------------------ decoding (csrc/transducer_step.hip)
+    def project_enc(self, enc_out):
+        """(T, D_enc) -> E = lin_enc(enc_out) (T, J) f32: one GEMM per utterance."""
+        with torch.no_grad():
+            return JointLinearFn.apply(enc_out, self._lin("lin_enc"))
+
+    def project_dec(self, dec_out):
+        """(n, D_dec) -> D = lin_dec(dec_out) (n, J) f32: the few-row GEMM."""
+        with torch.no_grad():
+            return JointLinearFn.apply(dec_out, self._lin("lin_dec"))
+
+    def _step_logits(self, E, frame, D):
+        """Launch A: -> (the (n, V) f32 logits of row i at frame[i], the slices' (max, sum exp) pairs)."""
+        _, bias, w = self._lin("lin_out")
+        (n, J), V = D.shape, w.shape[0]
+        if E.dim() != 2 or E.shape[1] != J or J != self.joint_space_size or frame.shape != (n,) \
+                or frame.dtype != torch.int32 or not frame.is_contiguous():
+            raise ValueError(f"E {tuple(E.shape)}, D {tuple(D.shape)}, frame {tuple(frame.shape)} {frame.dtype}")
+        E, D = f32c(E), f32c(D)
+        logits = torch.empty(n, V, device=D.device)
+        part = torch.empty(2 * n * -(-V // RNNT_STEP_SW), device=D.device)
+        lib.ea_rnnt_step_logits(dt(w), n, V, J, E.data_ptr(), E.stride(0), E.shape[0], frame.data_ptr(), D.data_ptr(),
+                                D.stride(0), w.data_ptr(), w.stride(0), bias.data_ptr(), logits.data_ptr(), V,
+                                part.data_ptr(), ops.stream())
+        return logits, part
+
+    def step(self, E, frame, D, k, want_logp=False):
+        """One joint step of n rows: row i is a hypothesis with D[i] = lin_dec(its decoder output) at frame
+        frame[i] (int32, on the device) of E (rows of lin_enc outputs).  -> JointStep: lse, lp_blank (n), the
+        top k of the non-blank log-probabilities (n, k) with their ids in 1 .. V-1 (descending, ties to the
+        lower id) and, with want_logp, the (n, V) log-probabilities.  Two launches, nothing synchronises."""
+        check_step(D.shape[0], k, self.lin_out.out_features)
+        with torch.no_grad():
+            logits, part = self._step_logits(E, frame, D)
+            n, V = logits.shape
+            packed = torch.empty(2 * n + 2 * n * k, device=D.device)  # lse | lp_blank | top values | top ids
+            ids = packed[2 * n + n * k:].view(torch.int32)
+            lib.ea_rnnt_step_select(n, V, k, logits.data_ptr(), V, part.data_ptr(), packed.data_ptr(),
+                                    packed[n:].data_ptr(), packed[2 * n:].data_ptr(), ids.data_ptr(), int(want_logp),
+                                    ops.stream())
+        return JointStep(packed[:n], packed[n:2 * n], packed[2 * n:2 * n + n * k].view(n, k), ids.view(n, k),
+                         logits if want_logp else None, packed)
+
     def forward(self, enc_out, dec_out):
-        raise NotImplementedError("espnet_amd JointNetwork: the (B, T, U, V) joint output is never built; the "
-                                  "loss takes the network itself (RNNTLoss.forward), decoding is not built")
+        """joint_network.py:43-59 at decoding time: enc_out_t (D_enc), dec_out (D_dec) -> the (V) logits."""
+        if enc_out.dim() != 1 or dec_out.dim() != 1 or torch.is_grad_enabled():
+            raise NotImplementedError("espnet_amd JointNetwork: the (B, T, U, V) joint output is never built; the "
+                                      "loss takes the network itself (RNNTLoss.forward); forward serves decoding: "
+                                      "1-D enc_out_t and dec_out under torch.no_grad()")
+        frame = torch.zeros(1, dtype=torch.int32, device=dec_out.device)
+        return self._step_logits(self.project_enc(enc_out[None]), frame, self.project_dec(dec_out[None]))[0][0]

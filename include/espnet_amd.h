@@ -1127,6 +1127,35 @@ int ea_rnnt_joint_dlogits(int dtype, int B, int T, int U1, int V, int J, const f
 int ea_rnnt_joint_dact(int B, int T, int U1, int J, const float* E, const float* D, const int* t_len, const int* u_len,
                        long bt0, long nbt, float* dh, float* dE, float* dD, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * RNN-Transducer decoding: one joint-network step over n rows (csrc/transducer_step.hip).  Replaces, per
+ * expanded hypothesis, JointNetwork.forward's tanh + lin_out, the log_softmax and the topk of
+ * espnet2/asr/transducer/beam_search_transducer.py:239-243 / :299-303.
+ *
+ * Row i (a running hypothesis, or an utterance of a greedy batch) stands at encoder frame frame[i]:
+ *   logit[i, v] = sum_j tanh(E[frame[i], j] + D[i, j]) * W[v, j] + bias[v],
+ * tanh rounded to `dtype` (EA_F32 / EA_BF16), f32 accumulation.  E (n_frames rows of lde >= J floats) and
+ * D (n rows of ldd >= J floats): f32, 16-B aligned rows (lde, ldd multiples of 4).  W (V, J) rows of ldw
+ * elements in `dtype`, 16-B aligned rows; bias (V) f32; frame (n) int32 in device memory, clamped to
+ * [0, n_frames).  J % 8 == 0 and J <= EA_RNNT_MAX_JOINT; 1 <= n <= EA_RNNT_STEP_MAX_ROWS; V >= 2;
+ * blank = 0.  V and J need not be tile multiples.
+ *
+ * ea_rnnt_step_logits: logits (n rows of ldl >= V floats) and, per vocabulary slice of EA_RNNT_STEP_SW
+ *   columns and row, the slice's (max, sum exp) pair: part holds 2 * n * ceil(V / EA_RNNT_STEP_SW) floats,
+ *   the caller's workspace.
+ * ea_rnnt_step_select: from the logits and part of the call above, lse[i], lp_blank[i] = logit[i, 0] -
+ *   lse[i], and the top k of logit[i, 1:] - lse[i]: top_val (n, k) descending, top_id (n, k) int32 in
+ *   1 .. V-1, ties to the lower id; 1 <= k <= min(EA_RNNT_STEP_MAX_K, V - 1).  want_logp != 0: the
+ *   logits rows become the f32 log-probabilities logit - lse, in place.
+ * A row's outputs do not depend on n or on the other rows, bit for bit.  No atomics, no host
+ * synchronisation, nothing allocated. */
+enum { EA_RNNT_STEP_MAX_ROWS = 64, EA_RNNT_STEP_MAX_K = 16, EA_RNNT_STEP_SW = 32 };
+int ea_rnnt_step_logits(int dtype, int n, int V, int J, const float* E, long lde, int n_frames, const int* frame,
+                        const float* D, long ldd, const void* W, long ldw, const float* bias, float* logits, long ldl,
+                        float* part, void* stream);
+int ea_rnnt_step_select(int n, int V, int k, float* logits, long ldl, const float* part, float* lse, float* lp_blank,
+                        float* top_val, int* top_id, int want_logp, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
