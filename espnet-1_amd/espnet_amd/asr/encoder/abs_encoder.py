@@ -56,7 +56,8 @@ def resolve_rel_pos_type(rel_pos_type, pos_enc_layer_type, attn_layer_type):
 
 
 class SubsamplingEncoder(AbsEncoder):
-    """Conv2dSubsampling `embed` -> `encoders` (a Sequential of `layer_class` blocks) ->
+    """`embed` (Conv2dSubsampling, Conv2dSubsampling2 or Conv2dSubsampling6) -> `encoders` (a
+    Sequential of `layer_class` blocks) ->
     `after_norm`.  A subclass sets `layer_class` and `_output_size` and builds the three modules."""
 
     layer_class = None
@@ -85,12 +86,18 @@ class SubsamplingEncoder(AbsEncoder):
         the reference's MultiSequential.forward (before any positional table is made).
         -> (x (B, T', d) f32, olens (B,) int64)."""
         B, T, _ = xs_pad.shape
-        if T < 7:  # check_short_utt, subsampling.py:31-43
+        embed = self.embed
+        limit = embed.limit
+        if T < limit:  # check_short_utt, subsampling.py:31-43
             raise TooShortUttError(f"has {T} frames and is too short for subsampling "
-                                   f"(it needs more than 7 frames), return empty results", T, 7)
+                                   f"(it needs more than {limit} frames), return empty results", T, limit)
         xs_pad = xs_pad.contiguous()
         olens = torch.empty(B, dtype=torch.long, device=xs_pad.device)
-        lib.ea_subsample_lens(B, T, ilens.data_ptr(), olens.data_ptr(), ops.stream())
+        if (embed.kernel, embed.stride) == (3, 2):
+            lib.ea_subsample_lens(B, T, ilens.data_ptr(), olens.data_ptr(), ops.stream())
+        else:
+            lib.ea_subsample_lens_ks(B, T, embed.kernel, embed.stride, ilens.data_ptr(), olens.data_ptr(),
+                                     ops.stream())
         x = self.embed(xs_pad, seed)
         if layerdrop_draw:
             multisequential_draw(len(self.encoders))

@@ -3,7 +3,7 @@
 Same constructor signature, option validation and state_dict layout; forward runs the
 HIP path: Conv2dSubsampling (SubsampleFn) -> N x ConformerBlockFn -> after_norm, with an
 InterCTCTapFn (layers/interctc.py) behind every layer in interctc_layer_idx.
-Only the configuration the reference's ASR recipes train (input_layer conv2d,
+Only the configuration the reference's ASR recipes train (input_layer conv2d, conv2d2 or conv2d6,
 rel_pos_type latest or legacy, (legacy_)rel_pos / (legacy_)rel_selfattn, macaron, conv module,
 normalize_before, intermediate / self-conditioned CTC) is implemented; other choices raise NotImplementedError
 instead of silently diverging.
@@ -20,7 +20,7 @@ from ...layers.common import LayerNormFn
 from ...layers.conformer import (ConvolutionModule, EncoderLayer, LayerNorm,
                                  PositionwiseFeedForward, RelPositionMultiHeadedAttention)
 from ...layers.interctc import InterCTCTapFn, TapState
-from ...layers.subsampling import Conv2dSubsampling, LegacyRelPositionalEncoding, RelPositionalEncoding
+from ...layers.subsampling import INPUT_LAYER_CLASSES, LegacyRelPositionalEncoding, RelPositionalEncoding
 from .abs_encoder import INPUT_LAYERS, AfterNorm, SubsamplingEncoder, resolve_rel_pos_type
 
 
@@ -95,7 +95,7 @@ class ConformerEncoder(SubsamplingEncoder):
         if (pos_enc_layer_type, selfattention_layer_type) not in (("rel_pos", "rel_selfattn"),
                                                                   ("legacy_rel_pos", "legacy_rel_selfattn")):
             unsupported.append(f"{pos_enc_layer_type}/{selfattention_layer_type}")
-        if input_layer != "conv2d":
+        if input_layer not in INPUT_LAYER_CLASSES:
             unsupported.append(f"input_layer={input_layer}")
         if positionwise_layer_type != "linear":
             unsupported.append(f"positionwise_layer_type={positionwise_layer_type}")
@@ -111,8 +111,8 @@ class ConformerEncoder(SubsamplingEncoder):
         if output_size % 8:
             raise ValueError("output_size must be a multiple of 8 (16-B aligned MFMA operands)")
         pos_enc_class = LegacyRelPositionalEncoding if legacy else RelPositionalEncoding
-        self.embed = Conv2dSubsampling(input_size, output_size, dropout_rate,
-                                       pos_enc_class(output_size, positional_dropout_rate, max_pos_emb_len))
+        self.embed = INPUT_LAYER_CLASSES[input_layer](
+            input_size, output_size, dropout_rate, pos_enc_class(output_size, positional_dropout_rate, max_pos_emb_len))
         self.normalize_before = normalize_before
         layers = []
         for lnum in range(num_blocks):

@@ -3,7 +3,8 @@
 
 Same constructor signature and state_dict layout (embed.conv.{0,2}, embed.out.0,
 encoders.{i}.{self_attn,feed_forward,norm1,norm2}, after_norm); forward runs the HIP
-path: Conv2dSubsampling with the absolute PositionalEncoding (subsampling.py:57-69 with
+path: Conv2dSubsampling (input_layer conv2d; Conv2dSubsampling2 / 6 for conv2d2 / conv2d6)
+with the absolute PositionalEncoding (subsampling.py:57-69 with
 PositionalEncoding(odim, dropout_rate) — the reference passes the encoder's dropout_rate,
 not positional_dropout_rate, to it) -> N x TransformerBlockFn -> after_norm.  Options the
 ASR recipes do not use (other input layers, conv1d feed-forward, concat_after,
@@ -18,7 +19,7 @@ from torch import nn
 
 from ...layers.conformer import MultiHeadedAttention, PositionwiseFeedForward
 from ...layers.decoder import PositionalEncoding
-from ...layers.subsampling import Conv2dSubsampling
+from ...layers.subsampling import INPUT_LAYER_CLASSES
 from ...layers.transformer import TransformerEncoderLayer
 from .abs_encoder import INPUT_LAYERS, AfterNorm, SubsamplingEncoder
 
@@ -53,7 +54,7 @@ class TransformerEncoder(SubsamplingEncoder):
         if positionwise_layer_type not in ("linear", "conv1d", "conv1d-linear"):
             raise NotImplementedError("Support only linear or conv1d.")
         unsupported = []
-        if input_layer != "conv2d":
+        if input_layer not in INPUT_LAYER_CLASSES:
             unsupported.append(f"input_layer={input_layer}")
         if positionwise_layer_type != "linear":
             unsupported.append(f"positionwise_layer_type={positionwise_layer_type}")
@@ -68,8 +69,8 @@ class TransformerEncoder(SubsamplingEncoder):
                                       "configuration only; unsupported: " + ", ".join(unsupported))
         if output_size % 8:
             raise ValueError("output_size must be a multiple of 8 (16-B aligned MFMA operands)")
-        self.embed = Conv2dSubsampling(input_size, output_size, dropout_rate,
-                                       PositionalEncoding(output_size, dropout_rate))
+        self.embed = INPUT_LAYER_CLASSES[input_layer](input_size, output_size, dropout_rate,
+                                                      PositionalEncoding(output_size, dropout_rate))
         self.normalize_before = normalize_before
         layers = []
         for lnum in range(num_blocks):

@@ -133,11 +133,15 @@ class LegacyRelPositionalEncoding(RelPositionalEncoding):
 class Conv2dSubsampling(nn.Module):
     """Parameter holder with the reference's names: conv.0 / conv.2 / out.0 (+ pos_enc)."""
 
+    kernel, stride = 3, 2  # of conv.2
+    limit = 7  # check_short_utt (subsampling.py:31-43): an utterance needs at least this many frames
+
     def __init__(self, idim, odim, dropout_rate, pos_enc=None):
         super().__init__()
-        self.conv = nn.Sequential(nn.Conv2d(1, odim, 3, 2), nn.ReLU(), nn.Conv2d(odim, odim, 3, 2), nn.ReLU())
+        k, s = self.kernel, self.stride
+        self.conv = nn.Sequential(nn.Conv2d(1, odim, 3, 2), nn.ReLU(), nn.Conv2d(odim, odim, k, s), nn.ReLU())
         self.F1 = (idim - 1) // 2
-        self.F2 = (self.F1 - 1) // 2
+        self.F2 = (self.F1 - k) // s + 1
         self.out = nn.Sequential(nn.Linear(odim * self.F2, odim),
                                  pos_enc if pos_enc is not None else RelPositionalEncoding(odim, dropout_rate))
         self.odim = odim
@@ -149,6 +153,26 @@ class Conv2dSubsampling(nn.Module):
 
     def forward(self, feats, seed):
         return SubsampleFn.apply(feats, self._anchor, self, seed, self.training)
+
+
+class Conv2dSubsampling2(Conv2dSubsampling):
+    """subsampling.py:94-149: conv.2 = Conv2d(odim, odim, 3, 1), out.0 over odim * ((idim-1)//2 - 2)."""
+
+    kernel, stride = 3, 1
+
+    def forward(self, feats, seed):
+        return ConvSubFn.apply(feats, self._anchor, self, seed, self.training)
+
+
+class Conv2dSubsampling6(Conv2dSubsampling2):
+    """subsampling.py:152-200: conv.2 = Conv2d(odim, odim, 5, 3), out.0 over odim * (((idim-1)//2 - 2)//3)."""
+
+    kernel, stride = 5, 3
+    limit = 11
+
+
+# input_layer name -> module (conformer_encoder.py:145-202); the other names are refused by the encoders
+INPUT_LAYER_CLASSES = {"conv2d": Conv2dSubsampling, "conv2d2": Conv2dSubsampling2, "conv2d6": Conv2dSubsampling6}
 
 
 def _out_linear(x2r, wl, b, pe, p, seed, B, T2, C):
@@ -166,6 +190,55 @@ def _out_linear(x2r, wl, b, pe, p, seed, B, T2, C):
     return y
 
 
+def _conv1_plain(b, feats, C):
+    """conv1 on the plain layout: im2col (P1 x 16) . W1p^T -> relu -> x1 (B*T1*F1, C).  -> (col1, x1)"""
+    cd = b.cd
+    B, T, Fin = feats.shape
+    dev = feats.device
+    P1 = B * ((T - 3) // 2 + 1) * ((Fin - 3) // 2 + 1)
+    col1 = empty(P1, 16, dtype=cd, device=dev)
+    lib.ea_im2col_conv1(B, T, Fin, feats.data_ptr(), col1.data_ptr(), ops.dt(col1), ops.stream())
+    w1 = empty(C, 16, dtype=cd, device=dev)
+    w1.zero_()
+    ops.scale_dropout(b.f("conv.0.weight", shape=(C, 9)), w1[:, :9])
+    x1 = empty(P1, C, dtype=cd, device=dev)
+    ops.linear(col1, w1, x1, epi=ops.make_epi(EPI_ACT, bias=b.f("conv.0.bias"), act=ACT_RELU))
+    return col1, x1
+
+
+def _conv1_plain_backward(b, dx1, col1, C):
+    """conv1's weight and bias gradients from the masked dx1 (P1, C) and the forward's col1."""
+    with ops.wgrad(dx1, col1, launches=True):
+        ops.colsum(dx1, b.g("conv.0.bias"))
+        ops.gemm(dx1, col1, b.g("conv.0.weight", shape=(C, 9)), M=C, N=9, K=dx1.shape[0],
+                 a_kmajor=0, b_kmajor=0, lda=C, ldb=16, ldc=9, epi=ops.make_epi(beta=1.0))
+
+
+def _out_weight(b, C, F2, dev):
+    """out.0's weight for the (t, f*C + c) row order: (d, C, F2) -> (d, F2, C)."""
+    wl = empty(C, F2 * C, dtype=b.cd, device=dev)
+    ops.permute3(b.f("out.0.weight"), wl, C, C, F2)
+    return wl
+
+
+def _out_backward(m, dy, x2, wl, dx2, B, T2, F2, p, seed):
+    """Backward of _out_linear: out.0's bias and weight gradients, and the gradient of conv.2's output
+    through its ReLU into dx2 (B*T2, F2*C)."""
+    b = m._b
+    C = m.odim
+    dev = dy.device
+    dv = empty(B * T2, C, dtype=b.cd, device=dev)
+    ops.scale_dropout_colsum(dy.reshape(B * T2, C).contiguous(), dv, b.g("out.0.bias"), scale=m.out[1].xscale,
+                             p=p, seed=seed)
+    x2r = x2.view(B * T2, F2 * C)
+    with ops.wgrad(dv, x2):
+        dwl = empty(C, F2 * C, device=dev)
+        gw = b.g("out.0.weight")
+        ops.linear_dw(dv, x2r, dwl, accumulate=False,  # then (d,F2,C) -> (d,C,F2) into the arena
+                      post=lambda: ops.permute3(dwl, gw, C, F2, C, accumulate=True))
+    ops.linear_dx(dv, wl, dx2, epi=ops.make_epi(EPI_DACT, act=ACT_RELU, aux=x2r))
+
+
 class SubsampleFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, feats, anchor, m: Conv2dSubsampling, seed, training):
@@ -180,15 +253,7 @@ class SubsampleFn(torch.autograd.Function):
         if _implicit_ok(cd, C):
             return SubsampleFn._forward_implicit(ctx, feats, m, seed, training, B, T, Fin, C, T1, F1, T2, F2)
         ctx.implicit = False
-        # conv1: im2col (P1 x 16) . W1p^T -> relu -> x1 (B,T1,F1,C)
-        P1 = B * T1 * F1
-        col1 = empty(P1, 16, dtype=cd, device=dev)
-        lib.ea_im2col_conv1(B, T, Fin, feats.data_ptr(), col1.data_ptr(), ops.dt(col1), ops.stream())
-        w1 = empty(C, 16, dtype=cd, device=dev)
-        w1.zero_()
-        ops.scale_dropout(b.f("conv.0.weight", shape=(C, 9)), w1[:, :9])
-        x1 = empty(P1, C, dtype=cd, device=dev)
-        ops.linear(col1, w1, x1, epi=ops.make_epi(EPI_ACT, bias=b.f("conv.0.bias"), act=ACT_RELU))
+        col1, x1 = _conv1_plain(b, feats, C)  # x1 (B,T1,F1,C)
         # conv2: im2col (P2 x 9C) . W2p^T -> relu -> x2 (B,T2,F2,C)
         P2 = B * T2 * F2
         col2 = empty(P2, 9 * C, dtype=cd, device=dev)
@@ -203,8 +268,7 @@ class SubsampleFn(torch.autograd.Function):
         if probe is not None:
             probe.end("conv2_gemm")
         # out.0 Linear on (t, f*C + c) rows, * sqrt(d), dropout (embedding.py:326)
-        wl = empty(C, F2 * C, dtype=cd, device=dev)
-        ops.permute3(b.f("out.0.weight"), wl, C, C, F2)  # (d, C, F2) -> (d, F2, C)
+        wl = _out_weight(b, C, F2, dev)
         p = pe.dropout_rate if training else 0.0
         y = _out_linear(x2.view(B * T2, F2 * C), wl, b, pe, p, seed, B, T2, C)
         ctx.m = m
@@ -243,8 +307,7 @@ class SubsampleFn(torch.autograd.Function):
                          x2.data_ptr(), ops.dt(x2), C, ctypes.byref(epi), ws.data_ptr(), ws.numel(), ops.stream())
         if probe is not None:
             probe.end("conv2_gemm")
-        wl = empty(C, F2 * C, dtype=cd, device=dev)
-        ops.permute3(b.f("out.0.weight"), wl, C, C, F2)  # (d, C, F2) -> (d, F2, C)
+        wl = _out_weight(b, C, F2, dev)
         p = pe.dropout_rate if training else 0.0
         y = _out_linear(x2.view(B * T2, F2 * C), wl, b, pe, p, seed, B, T2, C)
         ctx.m = m
@@ -264,21 +327,12 @@ class SubsampleFn(torch.autograd.Function):
         C = m.odim
         dev = dy.device
         P1, P2 = B * T1 * F1, B * T2 * F2
-        dv = empty(B * T2, C, dtype=cd, device=dev)
-        ops.scale_dropout_colsum(dy.reshape(B * T2, C).contiguous(), dv, b.g("out.0.bias"), scale=m.out[1].xscale,
-                                 p=p, seed=seed)
-        x2r = x2.view(B * T2, F2 * C)
-        with ops.wgrad(dv, x2):
-            dwl = empty(C, F2 * C, device=dev)
-            gw = b.g("out.0.weight")
-            ops.linear_dw(dv, x2r, dwl, accumulate=False,  # then (d,F2,C) -> (d,C,F2) into the arena
-                          post=lambda: ops.permute3(dwl, gw, C, F2, C, accumulate=True))
         # dY2 (relu-masked) with >= 64 zero rows after P2: the wgrad K padding and the dgrad
         # gather's off-grid rows
         K2 = rup(P2, 64)
         dx2 = empty(P2 + 128, C, dtype=cd, device=dev)
         dx2[P2:].zero_()
-        ops.linear_dx(dv, wl, dx2[:P2].view(B * T2, F2 * C), epi=ops.make_epi(EPI_DACT, act=ACT_RELU, aux=x2r))
+        _out_backward(m, dy, x2, wl, dx2[:P2].view(B * T2, F2 * C), B, T2, F2, p, seed)
         ws_side = None
         with ops.wgrad(dx2, x1p, launches=True):
             ops.colsum(dx2[:P2], b.g("conv.2.bias"))
@@ -367,17 +421,8 @@ class SubsampleFn(torch.autograd.Function):
         ctx.save = None
         C = m.odim
         dev = dy.device
-        dv = empty(B * T2, C, dtype=cd, device=dev)
-        ops.scale_dropout_colsum(dy.reshape(B * T2, C).contiguous(), dv, b.g("out.0.bias"), scale=m.out[1].xscale,
-                                 p=p, seed=seed)
-        x2r = x2.view(B * T2, F2 * C)
-        with ops.wgrad(dv, x2):
-            dwl = empty(C, F2 * C, device=dev)
-            gw = b.g("out.0.weight")
-            ops.linear_dw(dv, x2r, dwl, accumulate=False,  # then (d,F2,C) -> (d,C,F2) into the arena
-                          post=lambda: ops.permute3(dwl, gw, C, F2, C, accumulate=True))
         dx2 = empty(B * T2, F2 * C, dtype=cd, device=dev)
-        ops.linear_dx(dv, wl, dx2, epi=ops.make_epi(EPI_DACT, act=ACT_RELU, aux=x2r))
+        _out_backward(m, dy, x2, wl, dx2, B, T2, F2, p, seed)
         dx2 = dx2.view(-1, C)
         with ops.wgrad(dx2, col2):
             ops.colsum(dx2, b.g("conv.2.bias"))
@@ -392,9 +437,71 @@ class SubsampleFn(torch.autograd.Function):
         lib.ea_col2im_conv2(B, T1, F1, C, dcol2.data_ptr(), ops.dt(dcol2), x1.data_ptr(), dx1.data_ptr(),
                             ops.dt(dx1), ops.stream())
         del dcol2
-        with ops.wgrad(dx1, col1, launches=True):
-            ops.colsum(dx1, b.g("conv.0.bias"))
-            ops.gemm(dx1, col1, b.g("conv.0.weight", shape=(C, 9)), M=C, N=9, K=dx1.shape[0],
-                     a_kmajor=0, b_kmajor=0, lda=C, ldb=16, ldc=9, epi=ops.make_epi(beta=1.0))
+        _conv1_plain_backward(b, dx1, col1, C)
+        ops.grad_ready(b)
+        return None, None, None, None, None
+
+
+class ConvSubFn(torch.autograd.Function):
+    """Conv2dSubsampling2 / Conv2dSubsampling6 as one node: conv1 on SubsampleFn's plain-layout route,
+    conv.2 (kernel k, stride s, valid) on the strided implicit-GEMM kernels of csrc/conv_sub.hip over
+    the channel-last x1 (B, T1, F1, C), the output Linear through _out_linear."""
+
+    @staticmethod
+    def forward(ctx, feats, anchor, m: Conv2dSubsampling2, seed, training):
+        b = m._b
+        cd = b.cd
+        B, T, Fin = feats.shape
+        C, k, s = m.odim, m.kernel, m.stride
+        T1, F1 = (T - 3) // 2 + 1, (Fin - 3) // 2 + 1
+        T2, F2 = (T1 - k) // s + 1, (F1 - k) // s + 1
+        dev = feats.device
+        pe = m.out[1]
+        col1, x1 = _conv1_plain(b, feats, C)
+        geo = (B, T1, F1, C, k, s)  # the leading arguments of every ea_conv_sub_* entry point
+        w2 = empty(C, k * k * C, dtype=cd, device=dev)
+        ops.permute3(b.f("conv.2.weight"), w2, C, C, k * k)  # (Co,Ci,k*k) -> (Co,k*k,Ci)
+        x2 = empty(B * T2 * F2, C, dtype=cd, device=dev)
+        lib.ea_conv_sub_fwd(*geo, ops.dt(x2), x1.data_ptr(), w2.data_ptr(),
+                            b.f("conv.2.bias").data_ptr(), x2.data_ptr(), ops.stream())
+        wl = _out_weight(b, C, F2, dev)
+        p = pe.dropout_rate if training else 0.0
+        y = _out_linear(x2.view(B * T2, F2 * C), wl, b, pe, p, seed, B, T2, C)
+        ctx.m = m
+        ctx.meta = (B, T2, F2, p, seed, geo)
+        ctx.save = (col1, x1, x2, wl)
+        return y.view(B, T2, C)
+
+    @staticmethod
+    def backward(ctx, dy):
+        m = ctx.m
+        b = m._b
+        cd = b.cd
+        B, T2, F2, p, seed, geo = ctx.meta
+        col1, x1, x2, wl = ctx.save
+        ctx.save = None
+        C, kk = m.odim, m.kernel * m.kernel
+        dev = dy.device
+        dx2 = empty(B * T2, F2 * C, dtype=cd, device=dev)
+        _out_backward(m, dy, x2, wl, dx2, B, T2, F2, p, seed)
+        dx2 = dx2.view(-1, C)
+        with ops.wgrad(dx2, x1, launches=True):
+            ops.colsum(dx2, b.g("conv.2.bias"))
+            # pixel-range partials, summed in range order, then (Co,k*k,Ci) -> (Co,Ci,k*k) into the arena
+            n = ctypes.c_int(0)
+            lib.ea_conv_sub_wgrad_splits(*geo, ctypes.addressof(n))
+            part = empty(n.value, C * kk * C, device=dev)
+            lib.ea_conv_sub_wgrad(*geo, ops.dt(x1), x1.data_ptr(), dx2.data_ptr(), part.data_ptr(),
+                                  n.value, ops.stream())
+            dw2 = empty(C, kk * C, device=dev)
+            lib.ea_reduce_partials(n.value, C * kk * C, part.data_ptr(), C * kk * C, dw2.data_ptr(), 0, ops.stream())
+            ops.permute3(dw2, b.g("conv.2.weight"), C, kk, C, accumulate=True)
+        # input gradient: every stride-residue class in one launch, conv1's ReLU mask fused (aux = x1)
+        w2t = empty(C, kk * C, dtype=cd, device=dev)
+        ops.permute3(b.f("conv.2.weight"), w2t, 1, C, C * kk)  # (Co, Ci*k*k) -> (Ci, k*k, Co)
+        dx1 = empty(*x1.shape, dtype=cd, device=dev)
+        lib.ea_conv_sub_dgrad(*geo, ops.dt(dx1), dx2.data_ptr(), w2t.data_ptr(), x1.data_ptr(),
+                              dx1.data_ptr(), ops.stream())
+        _conv1_plain_backward(b, dx1, col1, C)
         ops.grad_ready(b)
         return None, None, None, None, None

@@ -387,6 +387,9 @@ int ea_specaug(int B, int T, int F, const float* x, const long long* lengths, co
 /* encoder_out_lens of Conv2dSubsampling from the sliced mask, subsampling.py:91 +
  * conformer_encoder.py:374. */
 int ea_subsample_lens(int B, int T, const long long* ilens, long long* olens, void* stream);
+/* the same for a second convolution of kernel k and stride s, the mask sliced
+ * [:, :, :-2:2][:, :, :-(k-1):s] (subsampling.py:149, 200): conv2d2 (3, 1), conv2d6 (5, 3). */
+int ea_subsample_lens_ks(int B, int T, int k, int s, const long long* ilens, long long* olens, void* stream);
 
 /* add_sos_eos + pad_list (transformer/add_sos_eos.py:12-31); ys_in/ys_out (B, L+1). */
 int ea_add_sos_eos(int B, int L, const long long* ys, long ldys, const long long* ylens, int sos,
@@ -1081,6 +1084,31 @@ int ea_vgg_conv1_fwd(int B, int H, int W, const float* x, const float* w, const 
                      void* stream);
 int ea_vgg_conv1_wgrad(int B, int H, int W, const float* x, const void* dy, int dtype, float* part, int nparts,
                        void* stream);
+
+/* ------------------------------------------------ Conv2dSubsampling2 / Conv2dSubsampling6 (csrc/conv_sub.hip) */
+
+/* The second convolution of input_layer conv2d2 / conv2d6 (transformer/subsampling.py:94-200): a valid
+ * C -> C convolution, kernel k, stride s, over channel-last x1 (B, T1, F1, C); (k, s) = (5, 3) or
+ * (3, 1), C % 8 == 0, T1 >= k, F1 >= k; T2 = (T1 - k) / s + 1, F2 likewise.  dtype EA_F32 (exact f32
+ * MFMA) or EA_BF16, f32 accumulation; every array but bias and part is in `dtype`, 16-B aligned.
+ * No im2col buffer and no atomics: equal inputs give bit-equal outputs.
+ *
+ * ea_conv_sub_fwd:   x2 (B, T2, F2, C) = relu(conv(x1, w) + bias), w (Co, k, k, Ci), bias (Co) f32.
+ * ea_conv_sub_dgrad: dx1 (B, T1, F1, C) = x1 > 0 ? conv_transpose(dy, w) : 0 with dy (B, T2, F2, C)
+ *   and wt (Ci, k, k, Co).  One launch over the stride-residue classes (t1 mod s, f1 mod s), the
+ *   longest K first; the rows t1 > s (T2 - 1) + k - 1 and columns f1 > s (F2 - 1) + k - 1 that no
+ *   window covers are written as exact zeros.
+ * ea_conv_sub_wgrad: part[r][co][kt][kf][ci] = sum over the output pixels p of range r of
+ *   dy[p][co] * x1[window of p at (kt, kf)][ci]; nsplit ranges of whole 32-pixel chunks, their
+ *   number from ea_conv_sub_wgrad_splits (at most 128); the caller sums the ranges in order
+ *   (ea_reduce_partials). */
+int ea_conv_sub_fwd(int B, int T1, int F1, int C, int k, int s, int dtype, const void* x1, const void* w,
+                    const float* bias, void* x2, void* stream);
+int ea_conv_sub_dgrad(int B, int T1, int F1, int C, int k, int s, int dtype, const void* dy, const void* wt,
+                      const void* x1, void* dx1, void* stream);
+int ea_conv_sub_wgrad_splits(int B, int T1, int F1, int C, int k, int s, int* nsplit);
+int ea_conv_sub_wgrad(int B, int T1, int F1, int C, int k, int s, int dtype, const void* x1, const void* dy,
+                      float* part, int nsplit, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * RNN-Transducer: the joint network fused with the RNN-T loss (csrc/transducer.hip).  Replaces
