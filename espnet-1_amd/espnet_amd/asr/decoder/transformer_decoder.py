@@ -136,14 +136,16 @@ class DecodeGraphs:
             kvl = kv[l]
             kvl.index_copy_(1, pos, qkv[:, d:].view(n, 1, 2 * d))
             O1, _ = _mha_fwd(qkv, kvl, kvl[:, :, d:], B=n, H=H, T1=1, T2=self.lcap, dk=dk, ldq=3 * d, ldk=2 * d,
-                             ldv=2 * d, klen=klen, causal=False, scale=scale, p=0.0, seed=0, cd=cd)
+                             ldv=2 * d, klen=klen, causal=False, scale=scale, p=0.0, seed=0, cd=cd,
+                             need_grad=False)
             x1 = empty(n, d, device=dev)
             ops.linear(O1, b.w(sa + "linear_out.weight"), x1,
                        epi=ops.make_epi(EPI_RESID, bias=b.f(sa + "linear_out.bias"), resid=x))
             q2 = empty(n, d, dtype=cd, device=dev)
             ln_linear(x1, nm + "norm2", b.w(xa + "linear_q.weight"), q2, ops.make_epi(bias=b.f(xa + "linear_q.bias")))
             O2, _ = _mha_fwd(q2, mkv[:, 2 * d * l:], mkv[:, 2 * d * l + d:], B=n, H=H, T1=1, T2=Tm, dk=dk,
-                             ldq=d, ldk=ldm, ldv=ldm, klen=hlens, causal=False, scale=scale, p=0.0, seed=0, cd=cd)
+                             ldq=d, ldk=ldm, ldv=ldm, klen=hlens, causal=False, scale=scale, p=0.0, seed=0, cd=cd,
+                             need_grad=False)
             x2 = empty(n, d, device=dev)
             ops.linear(O2, b.w(xa + "linear_out.weight"), x2,
                        epi=ops.make_epi(EPI_RESID, bias=b.f(xa + "linear_out.bias"), resid=x1))
@@ -354,7 +356,8 @@ class TransformerDecoder(AbsDecoder):
             ops.linear(xn1, b.w(sa + "linear_k.weight", sa + "linear_v.weight", shape=(2 * d, d)), kvl[:, pos],
                        epi=ops.make_epi(bias=b.f(sa + "linear_k.bias", sa + "linear_v.bias", shape=(2 * d,))))
             O1, _ = _mha_fwd(q, kvl, kvl[:, :, d:], B=n, H=H, T1=1, T2=L1, dk=dk, ldq=d, ldk=2 * d, ldv=2 * d,
-                             klen=klen, causal=False, scale=scale, p=0.0, seed=0, cd=cd)
+                             klen=klen, causal=False, scale=scale, p=0.0, seed=0, cd=cd,
+                             need_grad=False)
             x1 = empty(n, d, device=dev)
             ops.linear(O1, b.w(sa + "linear_out.weight"), x1,
                        epi=ops.make_epi(EPI_RESID, bias=b.f(sa + "linear_out.bias"), resid=x))
@@ -362,7 +365,8 @@ class TransformerDecoder(AbsDecoder):
             q2 = empty(n, d, dtype=cd, device=dev)
             ops.linear(xn2, b.w(xa + "linear_q.weight"), q2, epi=ops.make_epi(bias=b.f(xa + "linear_q.bias")))
             O2, _ = _mha_fwd(q2, mkv[:, 2 * d * l:], mkv[:, 2 * d * l + d:], B=n, H=H, T1=1, T2=Tm, dk=dk,
-                             ldq=d, ldk=ldm, ldv=ldm, klen=hlens, causal=False, scale=scale, p=0.0, seed=0, cd=cd)
+                             ldq=d, ldk=ldm, ldv=ldm, klen=hlens, causal=False, scale=scale, p=0.0, seed=0, cd=cd,
+                             need_grad=False)
             x2 = empty(n, d, device=dev)
             ops.linear(O2, b.w(xa + "linear_out.weight"), x2,
                        epi=ops.make_epi(EPI_RESID, bias=b.f(xa + "linear_out.bias"), resid=x1))

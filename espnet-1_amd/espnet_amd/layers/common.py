@@ -22,7 +22,7 @@ __all__ = ["Bound", "rup", "empty", "ops", "lib", "EPI_ACT", "EPI_DACT", "EPI_RE
            "EPI_STORE", "ACT_NONE", "ACT_RELU", "ACT_SWISH", "site_seed", "attn_fwd", "attn_bwd",
            "LayerNormFn", "ln_fwd", "ln_bwd", "math", "F32", "fused_attn_ok", "attn_dmask",
            "attn_fused_bwd", "dv_buf", "drop_arg", "site_dv", "multisequential_draw", "REL_LATEST",
-           "REL_LEGACY"]
+           "REL_LEGACY", "stream_attn_ok", "attn_stream_fwd"]
 
 F32 = torch.float32
 
@@ -44,6 +44,45 @@ def fused_attn_ok(cd, dk, T1, T2) -> bool:
     """The fused attention kernels (relattn.hip) take bf16 operands and head dim 64 (any
     lengths); other cases use the unfused path."""
     return FUSED_ATTN and cd == torch.bfloat16 and dk == 64 and T1 >= 1 and T2 >= 1
+
+
+SOFTMAX_MAX_KEYS = 2048  # ea_attn_softmax_fwd / _bwd keep a whole key row in registers
+
+
+def stream_attn_ok(cd, dk, T1, T2, need_grad) -> bool:
+    """The streaming f32 forward (attn_stream.hip) serves what neither other path can: the fused
+    kernels are not eligible and the key row is longer than the unfused softmax holds.  It has no
+    backward, so a forward that builds a graph at such a length is refused by name."""
+    if fused_attn_ok(cd, dk, T1, T2) or T2 <= SOFTMAX_MAX_KEYS:
+        return False
+    if need_grad:
+        raise NotImplementedError(
+            f"attention over {T2} keys: the training forward (a forward that requires gradients) is limited to "
+            f"{SOFTMAX_MAX_KEYS} keys outside bf16 with head dim 64 (here {str(cd).replace('torch.', '')}, head dim "
+            f"{dk}); inference is served at any length: run encode() / decoding under torch.no_grad()")
+    return True
+
+
+def attn_stream_fwd(q, k, v, *, B, H, T1, T2, dk, ldq, ldk, ldv, klen, causal, scale, cd, p=0.0, bd=None, ldbd=0,
+                    rel_mode=0, lse=False):
+    """ea_attn_stream_fwd: softmax(scale*(q k^T [+ rel_shift(bd)]) masked) @ v for all (b, h), keys
+    walked in tiles with an online softmax (no (T1, T2) buffer; any T2; head dim a multiple of 8 up
+    to 128).  Operands as attn_fwd's (f32 or bf16 row views).  Forward only, no dropout.  Returns
+    O (B*T1, H*dk) in cd, or (O, lse (B*H*T1) f32) with lse=True."""
+    if p > 0:
+        raise NotImplementedError(f"attn_stream_fwd has no dropout (attention dropout rate {p}): it is the "
+                                  "inference forward")
+    if dk % 8 or not 8 <= dk <= 128:
+        raise NotImplementedError(f"attn_stream_fwd: head dim {dk} is not a multiple of 8 in [8, 128]")
+    dev = q.device
+    O = empty(B * T1, H * dk, device=dev)
+    L = empty(B * H * T1, device=dev) if lse else None
+    lib.ea_attn_stream_fwd(B, H, T1, T2, dk, q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, ops.dt(q),
+                           ptr(bd), ldbd, ptr(klen), int(causal), float(scale), float(p), O.data_ptr(), H * dk,
+                           ptr(L), rel_mode, ops.stream())
+    if cd != F32:
+        O = ops.cast(O, cd)
+    return (O, L) if lse else O
 
 
 def attn_dmask(rows, T2, p, device):

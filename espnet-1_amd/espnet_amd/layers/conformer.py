@@ -166,7 +166,8 @@ class ConformerBlockFn(torch.autograd.Function):
         xn2, mu2, rs2 = ln_fwd(x1, b, "norm_mha", cd)
         A = "self_attn."
         mode = L.self_attn.rel_mode
-        O, s_core = rel_attn_fwd(b, A, xn2, pos, olens, B=B, T=T, H=H, rel_mode=mode, pa=pa, seed=sd(3))
+        O, s_core = rel_attn_fwd(b, A, xn2, pos, olens, B=B, T=T, H=H, rel_mode=mode, pa=pa, seed=sd(3),
+                                 need_grad=x.requires_grad)
         x2 = empty(N, d, device=dev)
         ops.linear(O, b.w(A + "linear_out.weight"), x2,
                    epi=ops.make_epi(EPI_RESID, bias=b.f(A + "linear_out.bias"), resid=x1,

@@ -16,14 +16,20 @@ import torch
 from torch import nn
 
 from .common import (ACT_RELU, EPI_ACT, EPI_DACT, EPI_RESID, EPI_STORE, F32, Bound, attn_bwd,
-                     attn_dmask, attn_fused_bwd, attn_fwd, empty, fused_attn_ok, lib, ln_bwd, ln_fwd, ops,
-                     site_seed, dv_buf, drop_arg, site_dv)
+                     attn_dmask, attn_fused_bwd, attn_fwd, attn_stream_fwd, empty, fused_attn_ok, lib, ln_bwd, ln_fwd,
+                     ops, site_seed, dv_buf, drop_arg, site_dv, stream_attn_ok)
 
 
-def _mha_fwd(q, k, v, *, B, H, T1, T2, dk, ldq, ldk, ldv, klen, causal, scale, p, seed, cd):
+def _mha_fwd(q, k, v, *, B, H, T1, T2, dk, ldq, ldk, ldv, klen, causal, scale, p, seed, cd, need_grad):
     """Scaled dot-product core of MultiHeadedAttention (attention.py:63-93) with the key
     padding (+ causal) mask: the fused flash kernel (relattn.hip, no positional term) when
-    eligible, else the unfused GEMM + softmax path.  Returns (O, saved state)."""
+    eligible, else the unfused GEMM + softmax path; without a backward to serve (need_grad False),
+    key rows longer than that path holds go to the streaming f32 kernel (attn_stream.hip).
+    Returns (O, saved state)."""
+    if stream_attn_ok(cd, dk, T1, T2, need_grad):
+        O = attn_stream_fwd(q, k, v, B=B, H=H, T1=T1, T2=T2, dk=dk, ldq=ldq, ldk=ldk, ldv=ldv, klen=klen,
+                            causal=causal, scale=scale, cd=cd, p=p)
+        return O, ("stream",)
     if fused_attn_ok(cd, dk, T1, T2):
         O = empty(B * T1, H * dk, dtype=cd, device=q.device)
         lse = empty(B * H * T1, device=q.device)
@@ -46,6 +52,8 @@ def _mha_bwd(st, dO, q, k, v, *, B, H, T1, T2, dk, ldq, ldk, ldv, klen, causal, 
                        dO=dO, lddo=H * dk, dq=dq, lddq=lddq, dk=dk_, lddk=lddk, dv=dv, lddv=lddv, dmask=dmask,
                        ldm=ldm)
         return
+    if st[0] == "stream":  # (a forward taken without need_grad: stream_attn_ok refuses the others)
+        raise NotImplementedError("the streaming attention forward (more than 2048 keys) has no backward")
     _, P, Pd, ldT = st
     attn_bwd(dO, q, k, v, P, Pd, ldT, B=B, H=H, T1=T1, T2=T2, dk=dk, ldq=ldq, ldk=ldk, ldv=ldv, scale=scale,
              p=p, seed=seed, cd=cd, dq=dq, lddq=lddq, dk_=dk_, lddk=lddk, dv=dv, lddv=lddv)
@@ -165,7 +173,7 @@ class DecoderFn(torch.autograd.Function):
                                                  sa + "linear_v.bias", shape=(3 * d,))))
             O1, st1 = _mha_fwd(qkv, qkv[:, d:], qkv[:, 2 * d:], B=B, H=H, T1=L, T2=L, dk=dk,
                                ldq=3 * d, ldk=3 * d, ldv=3 * d, klen=ys_in_lens, causal=True,
-                               scale=scale, p=p_sa, seed=sd(l, 1), cd=cd)
+                               scale=scale, p=p_sa, seed=sd(l, 1), cd=cd, need_grad=memory.requires_grad)
             x1 = empty(N, d, device=dev)
             ops.linear(O1, b.w(sa + "linear_out.weight"), x1,
                        epi=ops.make_epi(EPI_RESID, bias=b.f(sa + "linear_out.bias"), resid=x,
@@ -178,7 +186,7 @@ class DecoderFn(torch.autograd.Function):
             v2 = kv[:, 2 * d * l + d:]
             O2, st2 = _mha_fwd(q2, k2, v2, B=B, H=H, T1=L, T2=Tm, dk=dk, ldq=d, ldk=ldkv,
                                ldv=ldkv, klen=hlens, causal=False, scale=scale, p=p_src,
-                               seed=sd(l, 3), cd=cd)
+                               seed=sd(l, 3), cd=cd, need_grad=memory.requires_grad)
             x2 = empty(N, d, device=dev)
             ops.linear(O2, b.w(xa + "linear_out.weight"), x2,
                        epi=ops.make_epi(EPI_RESID, bias=b.f(xa + "linear_out.bias"), resid=x1,

@@ -134,7 +134,7 @@ class EBranchformerBlockFn(torch.autograd.Function):
         # ---- branch 1: rel-pos MHSA, no residual (:136-146)
         xna, mua, rsa = ln_fwd(x1, b, "norm_mha", cd)
         O, s_core = rel_attn_fwd(b, "attn.", xna, pos, olens, B=B, T=T, H=L.attn.h, rel_mode=REL_LATEST, pa=pa,
-                                 seed=sd(3))
+                                 seed=sd(3), need_grad=x.requires_grad)
         ops.linear(O, b.w("attn.linear_out.weight"), xc[:, :d],
                    epi=ops.make_epi(EPI_STORE, bias=b.f("attn.linear_out.bias"), drop_p=p, seed=sd(4)))
         # ---- branch 2: convolutional gating MLP (:149-157, cgmlp.py:110-118)

@@ -10,7 +10,8 @@ to it (`pre` / `A` select the holder).  A block's kernel launch order is the ord
 from __future__ import annotations
 
 from .common import (EPI_ACT, EPI_DACT, EPI_RESID, REL_LEGACY, attn_bwd, attn_dmask, attn_fused_bwd, attn_fwd,
-                     dbd_layout, empty, fused_attn_ok, lib, ln_bwd, ln_fwd, math, ops, rup, site_dv)
+                     attn_stream_fwd, dbd_layout, empty, fused_attn_ok, lib, ln_bwd, ln_fwd, math, ops, rup, site_dv,
+                     stream_attn_ok)
 
 
 # ----------------------------------------------------------------------------- feed-forward
@@ -58,10 +59,11 @@ def ffn_bwd(b, dx, x_in, saved, pre, ln_name, *, act, p_in, p_out, rscale, seed_
 
 
 # ----------------------------------------------------------------------------- rel-pos attention
-def rel_attn_fwd(b, A, xn, pos, olens, *, B, T, H, rel_mode, pa, seed):
+def rel_attn_fwd(b, A, xn, pos, olens, *, B, T, H, rel_mode, pa, seed, need_grad):
     """Rel-pos MHSA core (attention.py:262-305; REL_LEGACY: attention.py:114-206) on the parameters
     under prefix `A`: xn (N, d) cd -> O (N, d) cd, before linear_out.  pa / seed: the dropout on
-    the attention probabilities."""
+    the attention probabilities.  need_grad: the block's forward is part of a graph (a backward may
+    follow); without one, rows longer than the unfused softmax holds go to the streaming kernel."""
     cd = b.cd
     N, d = xn.shape
     dev = xn.device
@@ -73,6 +75,7 @@ def rel_attn_fwd(b, A, xn, pos, olens, *, B, T, H, rel_mode, pa, seed):
                epi=ops.make_epi(bias=b.f(A + "linear_q.bias", A + "linear_k.bias",
                                          A + "linear_v.bias", shape=(3 * d,))))
     fused = fused_attn_ok(cd, dk, T, T)
+    stream = stream_attn_ok(cd, dk, T, T, need_grad)  # (refuses a training forward it cannot serve)
     if rel_mode == REL_LEGACY and fused:
         # the fused backward's d(q+v) GEMM runs over every physical column of the shifted band
         # layout: `shift` zero rows in front of the table
@@ -114,6 +117,11 @@ def rel_attn_fwd(b, A, xn, pos, olens, *, B, T, H, rel_mode, pa, seed):
         bd = empty(H * B * T * ldbd, device=dev)
         ops.gemm(qv, pp, bd, M=T, N=P2, K=dk, a_kmajor=1, b_kmajor=1, lda=d, ldb=d, ldc=ldbd,
                  batch=B, nh=H, sA=(T * d, dk), sB=(0, dk), sC=(T * ldbd, B * T * ldbd), splitk=False)
+        if stream:  # the band GEMM above, then one kernel that never builds the (T, T) scores
+            O = attn_stream_fwd(qu, qkv[:, d:], qkv[:, 2 * d:], B=B, H=H, T1=T, T2=T, dk=dk, ldq=d, ldk=3 * d,
+                                ldv=3 * d, klen=olens, causal=False, scale=scale, cd=cd, p=pa, bd=bd, ldbd=ldbd,
+                                rel_mode=rel_mode)
+            return O, (qkv, pp, ("stream",), scale, 0)
         O, P, Pd, ldT = attn_fwd(qu, qkv[:, d:], qkv[:, 2 * d:], B=B, H=H, T1=T, T2=T, dk=dk,
                                  ldq=d, ldk=3 * d, ldv=3 * d, klen=olens, causal=False, scale=scale,
                                  p=pa, seed=seed, cd=cd, bd=bd, ldbd=ldbd, rel_mode=rel_mode)
@@ -168,6 +176,8 @@ def rel_attn_bwd(b, A, dO, xn, O, saved, pos, olens, *, B, T, H, rel_mode, pa, s
         else:
             ops.reduce_rows(part[B * nqb * d:], B * nqb, d, d, b.g(A + "pos_bias_v", shape=(d,)))
     else:
+        if s_core[0] == "stream":  # (a forward taken without need_grad: stream_attn_ok refuses the others)
+            raise NotImplementedError("the streaming attention forward (more than 2048 keys) has no backward")
         _, qu, qv, P, Pd = s_core
         dbd = empty(H * B * T * ldbd, dtype=cd, device=dev)
         attn_bwd(dO, qu, qkv[:, d:], qkv[:, 2 * d:], P, Pd, ldT, B=B, H=H, T1=T, T2=T, dk=dk,

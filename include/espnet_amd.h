@@ -624,6 +624,24 @@ int ea_attn_fused_bwd2_mode(int B, int H, int T1, int T2, int dk, const void* q,
  * the band copied likewise: zeros); nhb = H*B blocks of T1 rows, bf16, out != dbd. */
 int ea_attn_legacy_band(long nhb, int T1, const void* dbd, void* out, long lddbd, void* stream);
 
+/* Streaming forward attention in f32 (f32 MFMA, online softmax over key tiles of 64): the forward
+ * of inference for what the kernels above do not take — f32 operands, head dims other than 64,
+ * key rows longer than ea_attn_softmax_fwd's 2048.  No buffer of size T1 x T2 exists.
+ *   s[i,j] = (q_i·k_j + BD[i + (rel_mode == EA_REL_LEGACY && j > i)][T1-1-i+j]) * scale
+ * masked as above (key j valid iff j < klen[b], and j <= i when causal; klen NULL = T2, values
+ * outside [0, T2] are clamped), O = softmax(s) v, lse[(b*H + h)*T1 + i] = logsumexp_j s[i,j]
+ * (lse NULL: not written).  A row with no valid key gives O = 0, lse = -inf.
+ *  q (B*T1 rows), k, v (B*T2 rows): `dtype` (EA_F32 / EA_BF16, widened to f32), head h at column
+ *    h*dk, row strides ldq / ldk / ldv % 4 == 0, 16-B aligned bases.  O: f32, B*T1 rows of ldo.
+ *  BD (or NULL): the raw band [h][b][i][ldBD] f32, 2*T1-1 columns; needs T1 == T2.  EA_REL_LEGACY
+ *    needs BD and no causal mask.
+ *  Any T1 >= 0, T2 >= 1; dk % 8 == 0, 8 <= dk <= 128.  p is the attention dropout rate: there is no
+ *  dropout here, p > 0 is EA_ERR_BAD_ARG.  No backward. */
+int ea_attn_stream_fwd(int B, int H, int T1, int T2, int dk, const void* q, long ldq, const void* k,
+                       long ldk, const void* v, long ldv, int dtype, const float* BD, long ldBD,
+                       const long long* klen, int causal, float scale, float p, float* O, long ldo,
+                       float* lse, int rel_mode, void* stream);
+
 /* ---------------------------------------------------------------- losses */
 
 /* CTC forward (ctc.py:52-97 builtin; torch CTCLoss reduction=none, zero_infinity=True,
