@@ -22,7 +22,8 @@ __all__ = ["Bound", "rup", "empty", "ops", "lib", "EPI_ACT", "EPI_DACT", "EPI_RE
            "EPI_STORE", "ACT_NONE", "ACT_RELU", "ACT_SWISH", "site_seed", "attn_fwd", "attn_bwd",
            "LayerNormFn", "ln_fwd", "ln_bwd", "math", "F32", "fused_attn_ok", "attn_dmask",
            "attn_fused_bwd", "dv_buf", "drop_arg", "site_dv", "multisequential_draw", "REL_LATEST",
-           "REL_LEGACY", "stream_attn_ok", "attn_stream_fwd"]
+           "REL_LEGACY", "stream_attn_ok", "attn_stream_fwd", "stream_attn_train_ok", "attn_stream_train_fwd",
+           "attn_stream_bwd"]
 
 F32 = torch.float32
 
@@ -38,6 +39,9 @@ def empty(*shape, dtype=F32, device="cuda"):
 
 
 FUSED_ATTN = os.environ.get("EA_FUSED_ATTN", "1") != "0"
+# Training attention outside the fused kernels on the streaming forward + backward (attn_stream.hip):
+# no (T1, T2) buffer, any number of keys.  Off: the unfused GEMM -> softmax -> GEMM chain.
+STREAM_ATTN_TRAIN = os.environ.get("EA_STREAM_ATTN_TRAIN", "0") == "1"
 
 
 def fused_attn_ok(cd, dk, T1, T2) -> bool:
@@ -49,17 +53,30 @@ def fused_attn_ok(cd, dk, T1, T2) -> bool:
 SOFTMAX_MAX_KEYS = 2048  # ea_attn_softmax_fwd / _bwd keep a whole key row in registers
 
 
+def stream_attn_train_ok(cd, dk, T1, T2, need_grad) -> bool:
+    """With STREAM_ATTN_TRAIN, every attention forward that requires gradients and is not eligible for
+    the fused kernels takes attn_stream_train_fwd / attn_stream_bwd, at any length.  Ask before
+    stream_attn_ok."""
+    if not (STREAM_ATTN_TRAIN and need_grad) or fused_attn_ok(cd, dk, T1, T2):
+        return False
+    if dk % 8 or not 8 <= dk <= 128:
+        raise NotImplementedError(f"EA_STREAM_ATTN_TRAIN=1: head dim {dk} is not a multiple of 8 in [8, 128]")
+    return True
+
+
 def stream_attn_ok(cd, dk, T1, T2, need_grad) -> bool:
-    """The streaming f32 forward (attn_stream.hip) serves what neither other path can: the fused
-    kernels are not eligible and the key row is longer than the unfused softmax holds.  It has no
-    backward, so a forward that builds a graph at such a length is refused by name."""
+    """The streaming inference forward (attn_stream_fwd) serves what neither other path can: the fused
+    kernels are not eligible and the key row is longer than the unfused softmax holds.  A forward that
+    builds a graph at such a length needs the streaming training path (stream_attn_train_ok); without
+    that switch it is refused by name."""
     if fused_attn_ok(cd, dk, T1, T2) or T2 <= SOFTMAX_MAX_KEYS:
         return False
     if need_grad:
         raise NotImplementedError(
             f"attention over {T2} keys: the training forward (a forward that requires gradients) is limited to "
             f"{SOFTMAX_MAX_KEYS} keys outside bf16 with head dim 64 (here {str(cd).replace('torch.', '')}, head dim "
-            f"{dk}); inference is served at any length: run encode() / decoding under torch.no_grad()")
+            f"{dk}); inference is served at any length: run encode() / decoding under torch.no_grad(); "
+            "EA_STREAM_ATTN_TRAIN=1 trains at any length on the streaming kernels")
     return True
 
 
@@ -83,6 +100,37 @@ def attn_stream_fwd(q, k, v, *, B, H, T1, T2, dk, ldq, ldk, ldv, klen, causal, s
     if cd != F32:
         O = ops.cast(O, cd)
     return (O, L) if lse else O
+
+
+def attn_stream_train_fwd(q, k, v, *, B, H, T1, T2, dk, ldq, ldk, ldv, klen, causal, scale, cd, p, seed, bd=None,
+                          ldbd=0, rel_mode=0):
+    """ea_attn_stream_fwd_train: attn_stream_fwd with dropout on the probabilities, the keep law and
+    salt of attn_fwd (the same (p, seed) drops the same elements).  Returns O (B*T1, H*dk) in cd and
+    lse (B*H*T1) f32 of the undropped scores, what attn_stream_bwd needs beside the operands."""
+    if dk % 8 or not 8 <= dk <= 128:
+        raise NotImplementedError(f"attn_stream_train_fwd: head dim {dk} is not a multiple of 8 in [8, 128]")
+    dev = q.device
+    O = empty(B * T1, H * dk, device=dev)
+    L = empty(B * H * T1, device=dev)
+    lib.ea_attn_stream_fwd_train(B, H, T1, T2, dk, q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv,
+                                 ops.dt(q), ptr(bd), ldbd, ptr(klen), int(causal), float(scale), float(p), seed,
+                                 O.data_ptr(), H * dk, L.data_ptr(), rel_mode, ops.stream())
+    if cd != F32:
+        O = ops.cast(O, cd)
+    return O, L
+
+
+def attn_stream_bwd(dO, q, k, v, lse, *, B, H, T1, T2, dk, ldq, ldk, ldv, klen, causal, scale, p, seed,
+                    dq, lddq, dk_, lddk, dv, lddv, bd=None, ldbd=0, dbd=None, lddbd=0, rel_mode=0):
+    """ea_attn_stream_bwd: backward of attn_stream_train_fwd from its operands, lse and dO
+    ((B*T1, H*dk) cd); the scores are recomputed, no (T1, T2) buffer.  Writes dq, dk_, dv (attn_bwd's
+    contracts) and, with the raw band bd, its gradient dbd [h][b][i][lddbd] in cd, every one of the
+    2*T1-1 columns.  The workspace (2*B*H*T1 f32) is a stream-ordered allocation."""
+    ws = empty(max(2 * B * H * T1, 1), device=dO.device)
+    lib.ea_attn_stream_bwd(B, H, T1, T2, dk, q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, ops.dt(q),
+                           ptr(bd), ldbd, ptr(klen), int(causal), float(scale), float(p), seed,
+                           lse.data_ptr(), dO.data_ptr(), H * dk, dq.data_ptr(), lddq, dk_.data_ptr(), lddk,
+                           dv.data_ptr(), lddv, ptr(dbd), lddbd, ws.data_ptr(), ws.numel() * 4, rel_mode, ops.stream())
 
 
 def attn_dmask(rows, T2, p, device):

@@ -16,16 +16,22 @@ import torch
 from torch import nn
 
 from .common import (ACT_RELU, EPI_ACT, EPI_DACT, EPI_RESID, EPI_STORE, F32, Bound, attn_bwd,
-                     attn_dmask, attn_fused_bwd, attn_fwd, attn_stream_fwd, empty, fused_attn_ok, lib, ln_bwd, ln_fwd,
-                     ops, site_seed, dv_buf, drop_arg, site_dv, stream_attn_ok)
+                     attn_dmask, attn_fused_bwd, attn_fwd, attn_stream_bwd, attn_stream_fwd, attn_stream_train_fwd,
+                     empty, fused_attn_ok, lib, ln_bwd, ln_fwd, ops, site_seed, dv_buf, drop_arg, site_dv,
+                     stream_attn_ok, stream_attn_train_ok)
 
 
 def _mha_fwd(q, k, v, *, B, H, T1, T2, dk, ldq, ldk, ldv, klen, causal, scale, p, seed, cd, need_grad):
     """Scaled dot-product core of MultiHeadedAttention (attention.py:63-93) with the key
     padding (+ causal) mask: the fused flash kernel (relattn.hip, no positional term) when
     eligible, else the unfused GEMM + softmax path; without a backward to serve (need_grad False),
-    key rows longer than that path holds go to the streaming f32 kernel (attn_stream.hip).
+    key rows longer than that path holds go to the streaming f32 kernel (attn_stream.hip); with
+    STREAM_ATTN_TRAIN the forwards that need one and are not fused go to its training pair.
     Returns (O, saved state)."""
+    if stream_attn_train_ok(cd, dk, T1, T2, need_grad):
+        O, lse = attn_stream_train_fwd(q, k, v, B=B, H=H, T1=T1, T2=T2, dk=dk, ldq=ldq, ldk=ldk, ldv=ldv, klen=klen,
+                                       causal=causal, scale=scale, cd=cd, p=p, seed=seed)
+        return O, ("stream_train", lse)
     if stream_attn_ok(cd, dk, T1, T2, need_grad):
         O = attn_stream_fwd(q, k, v, B=B, H=H, T1=T1, T2=T2, dk=dk, ldq=ldq, ldk=ldk, ldv=ldv, klen=klen,
                             causal=causal, scale=scale, cd=cd, p=p)
@@ -52,8 +58,11 @@ def _mha_bwd(st, dO, q, k, v, *, B, H, T1, T2, dk, ldq, ldk, ldv, klen, causal, 
                        dO=dO, lddo=H * dk, dq=dq, lddq=lddq, dk=dk_, lddk=lddk, dv=dv, lddv=lddv, dmask=dmask,
                        ldm=ldm)
         return
-    if st[0] == "stream":  # (a forward taken without need_grad: stream_attn_ok refuses the others)
-        raise NotImplementedError("the streaming attention forward (more than 2048 keys) has no backward")
+    if st[0] == "stream_train":
+        attn_stream_bwd(dO, q, k, v, st[1], B=B, H=H, T1=T1, T2=T2, dk=dk, ldq=ldq, ldk=ldk, ldv=ldv, klen=klen,
+                        causal=causal, scale=scale, p=p, seed=seed, dq=dq, lddq=lddq, dk_=dk_, lddk=lddk,
+                        dv=dv, lddv=lddv)
+        return
     _, P, Pd, ldT = st
     attn_bwd(dO, q, k, v, P, Pd, ldT, B=B, H=H, T1=T1, T2=T2, dk=dk, ldq=ldq, ldk=ldk, ldv=ldv, scale=scale,
              p=p, seed=seed, cd=cd, dq=dq, lddq=lddq, dk_=dk_, lddk=lddk, dv=dv, lddv=lddv)

@@ -10,8 +10,8 @@ to it (`pre` / `A` select the holder).  A block's kernel launch order is the ord
 from __future__ import annotations
 
 from .common import (EPI_ACT, EPI_DACT, EPI_RESID, REL_LEGACY, attn_bwd, attn_dmask, attn_fused_bwd, attn_fwd,
-                     attn_stream_fwd, dbd_layout, empty, fused_attn_ok, lib, ln_bwd, ln_fwd, math, ops, rup, site_dv,
-                     stream_attn_ok)
+                     attn_stream_bwd, attn_stream_fwd, attn_stream_train_fwd, dbd_layout, empty, fused_attn_ok, lib,
+                     ln_bwd, ln_fwd, math, ops, rup, site_dv, stream_attn_ok, stream_attn_train_ok)
 
 
 # ----------------------------------------------------------------------------- feed-forward
@@ -75,7 +75,9 @@ def rel_attn_fwd(b, A, xn, pos, olens, *, B, T, H, rel_mode, pa, seed, need_grad
                epi=ops.make_epi(bias=b.f(A + "linear_q.bias", A + "linear_k.bias",
                                          A + "linear_v.bias", shape=(3 * d,))))
     fused = fused_attn_ok(cd, dk, T, T)
-    stream = stream_attn_ok(cd, dk, T, T, need_grad)  # (refuses a training forward it cannot serve)
+    train_stream = stream_attn_train_ok(cd, dk, T, T, need_grad)
+    # (refuses a training forward it cannot serve)
+    stream = not train_stream and stream_attn_ok(cd, dk, T, T, need_grad)
     if rel_mode == REL_LEGACY and fused:
         # the fused backward's d(q+v) GEMM runs over every physical column of the shifted band
         # layout: `shift` zero rows in front of the table
@@ -122,6 +124,11 @@ def rel_attn_fwd(b, A, xn, pos, olens, *, B, T, H, rel_mode, pa, seed, need_grad
                                 ldv=3 * d, klen=olens, causal=False, scale=scale, cd=cd, p=pa, bd=bd, ldbd=ldbd,
                                 rel_mode=rel_mode)
             return O, (qkv, pp, ("stream",), scale, 0)
+        if train_stream:  # keeps q+u, q+v and lse; the band is recomputed in the backward
+            O, lse = attn_stream_train_fwd(qu, qkv[:, d:], qkv[:, 2 * d:], B=B, H=H, T1=T, T2=T, dk=dk, ldq=d,
+                                           ldk=3 * d, ldv=3 * d, klen=olens, causal=False, scale=scale, cd=cd, p=pa,
+                                           seed=seed, bd=bd, ldbd=ldbd, rel_mode=rel_mode)
+            return O, (qkv, pp, ("stream_train", qu, qv, lse), scale, 0)
         O, P, Pd, ldT = attn_fwd(qu, qkv[:, d:], qkv[:, 2 * d:], B=B, H=H, T1=T, T2=T, dk=dk,
                                  ldq=d, ldk=3 * d, ldv=3 * d, klen=olens, causal=False, scale=scale,
                                  p=pa, seed=seed, cd=cd, bd=bd, ldbd=ldbd, rel_mode=rel_mode)
@@ -176,14 +183,25 @@ def rel_attn_bwd(b, A, dO, xn, O, saved, pos, olens, *, B, T, H, rel_mode, pa, s
         else:
             ops.reduce_rows(part[B * nqb * d:], B * nqb, d, d, b.g(A + "pos_bias_v", shape=(d,)))
     else:
-        if s_core[0] == "stream":  # (a forward taken without need_grad: stream_attn_ok refuses the others)
-            raise NotImplementedError("the streaming attention forward (more than 2048 keys) has no backward")
-        _, qu, qv, P, Pd = s_core
         dbd = empty(H * B * T * ldbd, dtype=cd, device=dev)
-        attn_bwd(dO, qu, qkv[:, d:], qkv[:, 2 * d:], P, Pd, ldT, B=B, H=H, T1=T, T2=T, dk=dk,
-                 ldq=d, ldk=3 * d, ldv=3 * d, scale=scale, p=pa, seed=seed, cd=cd,
-                 dq=dqkv, lddq=3 * d, dk_=dqkv[:, d:], lddk=3 * d, dv=dqkv[:, 2 * d:], lddv=3 * d,
-                 dbd=dbd, ldbd=ldbd, rel_mode=rel_mode)
+        if s_core[0] == "stream_train":
+            # the forward's band GEMM again (the band is the largest tensor of the block at long T, so it
+            # is not kept), then the two streaming passes
+            _, qu, qv, lse = s_core
+            bd = empty(H * B * T * ldbd, device=dev)
+            ops.gemm(qv, pp, bd, M=T, N=P2, K=dk, a_kmajor=1, b_kmajor=1, lda=d, ldb=d, ldc=ldbd,
+                     batch=B, nh=H, sA=(T * d, dk), sB=(0, dk), sC=(T * ldbd, B * T * ldbd), splitk=False)
+            attn_stream_bwd(dO, qu, qkv[:, d:], qkv[:, 2 * d:], lse, B=B, H=H, T1=T, T2=T, dk=dk, ldq=d,
+                            ldk=3 * d, ldv=3 * d, klen=olens, causal=False, scale=scale, p=pa, seed=seed,
+                            dq=dqkv, lddq=3 * d, dk_=dqkv[:, d:], lddk=3 * d, dv=dqkv[:, 2 * d:], lddv=3 * d,
+                            bd=bd, ldbd=ldbd, dbd=dbd, lddbd=ldbd, rel_mode=rel_mode)
+            del bd
+        else:
+            _, qu, qv, P, Pd = s_core
+            attn_bwd(dO, qu, qkv[:, d:], qkv[:, 2 * d:], P, Pd, ldT, B=B, H=H, T1=T, T2=T, dk=dk,
+                     ldq=d, ldk=3 * d, ldv=3 * d, scale=scale, p=pa, seed=seed, cd=cd,
+                     dq=dqkv, lddq=3 * d, dk_=dqkv[:, d:], lddk=3 * d, dv=dqkv[:, 2 * d:], lddv=3 * d,
+                     dbd=dbd, ldbd=ldbd, rel_mode=rel_mode)
         # q_u = q + u: du = sum dq_u ; q_v = q + v path: dq_v = dBD . p_h, dv_bias = sum dq_v
         dqv = empty(N, d, dtype=cd, device=dev)
         ops.gemm(dbd, pp, dqv, M=T, N=dk, K=P2, a_kmajor=1, b_kmajor=0, lda=ldbd, ldb=d, ldc=d,

@@ -636,11 +636,37 @@ int ea_attn_legacy_band(long nhb, int T1, const void* dbd, void* out, long lddbd
  *  BD (or NULL): the raw band [h][b][i][ldBD] f32, 2*T1-1 columns; needs T1 == T2.  EA_REL_LEGACY
  *    needs BD and no causal mask.
  *  Any T1 >= 0, T2 >= 1; dk % 8 == 0, 8 <= dk <= 128.  p is the attention dropout rate: there is no
- *  dropout here, p > 0 is EA_ERR_BAD_ARG.  No backward. */
+ *  dropout here, p > 0 is EA_ERR_BAD_ARG: the inference entry. */
 int ea_attn_stream_fwd(int B, int H, int T1, int T2, int dk, const void* q, long ldq, const void* k,
                        long ldk, const void* v, long ldv, int dtype, const float* BD, long ldBD,
                        const long long* klen, int causal, float scale, float p, float* O, long ldo,
                        float* lse, int rel_mode, void* stream);
+/* The training forward: ea_attn_stream_fwd with attention dropout, 0 <= p < 1, under `seed` and the
+ * process-wide salt.  Element (i, j) of (b, h) is kept by the law of every other attention path
+ * (attention row (b*H + h)*T1 + i, key j), so the same (p, seed) drops the same elements as
+ * ea_attn_softmax_fwd and the fused kernels.  O = (softmax(s) * m / (1-p)) v; lse, always written, is
+ * that of the undropped scores. */
+int ea_attn_stream_fwd_train(int B, int H, int T1, int T2, int dk, const void* q, long ldq, const void* k,
+                             long ldk, const void* v, long ldv, int dtype, const float* BD, long ldBD,
+                             const long long* klen, int causal, float scale, float p, unsigned long long seed,
+                             float* O, long ldo, float* lse, int rel_mode, void* stream);
+/* Backward of ea_attn_stream_fwd_train from its operands, lse and dO (`dtype`, row stride lddo): the
+ * scores are recomputed tile by tile, nothing of size T1 x T2 exists.
+ *   P = exp(s - lse) (0 for masked keys and rows with lse = -inf),
+ *   D_i = dO_i·O_i, taken as sum_j m/(1-p) P_ij dO_i·v_j in a sweep of its own (O is not an operand),
+ *   dS = scale * P * (m/(1-p) * dO_i·v_j - D_i),  dv_j = sum_i m/(1-p) P dO_i,
+ *   dq_i = sum_j dS k_j,  dk_j = sum_i dS q_i,  dbd[i + (legacy && j > i)][T1-1-i+j] = dS_ij.
+ *  dq (B*T1 rows), dkout, dvout (B*T2 rows; rows at or past klen are zeros): `dtype`, head h at column
+ *    h*dk, row strides lddq / lddk / lddv.  dbd (needed iff BD): [h][b][i][lddbd] in `dtype`, all 2*T1-1
+ *    columns of every row written (zeros where no valid (i, j) lands).
+ *  ws: 2*B*H*T1 floats of workspace (the row sums D and C), ws_bytes its size.  Three launches on `stream`,
+ *    no atomics. */
+int ea_attn_stream_bwd(int B, int H, int T1, int T2, int dk, const void* q, long ldq, const void* k,
+                       long ldk, const void* v, long ldv, int dtype, const float* BD, long ldBD,
+                       const long long* klen, int causal, float scale, float p, unsigned long long seed,
+                       const float* lse, const void* dO, long lddo, void* dq, long lddq, void* dkout,
+                       long lddk, void* dvout, long lddv, void* dbd, long lddbd,
+                       float* ws, long ws_bytes, int rel_mode, void* stream);
 
 /* ---------------------------------------------------------------- losses */
 
