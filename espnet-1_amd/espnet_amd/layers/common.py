@@ -23,7 +23,7 @@ __all__ = ["Bound", "rup", "empty", "ops", "lib", "EPI_ACT", "EPI_DACT", "EPI_RE
            "LayerNormFn", "ln_fwd", "ln_bwd", "math", "F32", "fused_attn_ok", "attn_dmask",
            "attn_fused_bwd", "dv_buf", "drop_arg", "site_dv", "multisequential_draw", "REL_LATEST",
            "REL_LEGACY", "stream_attn_ok", "attn_stream_fwd", "stream_attn_train_ok", "attn_stream_train_fwd",
-           "attn_stream_bwd"]
+           "attn_stream_bwd", "stream_attn_cores"]
 
 F32 = torch.float32
 
@@ -41,7 +41,26 @@ def empty(*shape, dtype=F32, device="cuda"):
 FUSED_ATTN = os.environ.get("EA_FUSED_ATTN", "1") != "0"
 # Training attention outside the fused kernels on the streaming forward + backward (attn_stream.hip):
 # no (T1, T2) buffer, any number of keys.  Off: the unfused GEMM -> softmax -> GEMM chain.
-STREAM_ATTN_TRAIN = os.environ.get("EA_STREAM_ATTN_TRAIN", "0") == "1"
+# EA_STREAM_ATTN_TRAIN=bf16: as =1, and bf16 operands take the bf16-MFMA kernels (attn_stream_bf16.hip), the
+# inference forward beyond 2048 keys included; f32 operands always multiply on the f32 matrix cores.
+STREAM_ATTN_TRAIN = os.environ.get("EA_STREAM_ATTN_TRAIN", "0") in ("1", "bf16")
+STREAM_ATTN_CORES = "bf16" if os.environ.get("EA_STREAM_ATTN_TRAIN", "0") == "bf16" else "f32"
+
+
+def stream_attn_cores(cd) -> str:
+    """The `cores` of the streaming wrappers below for operands of compute dtype cd under the switch."""
+    return "bf16" if STREAM_ATTN_CORES == "bf16" and cd == torch.bfloat16 else "f32"
+
+
+def _stream_entry(name, cores, q):
+    """The f32-MFMA entry `ea_attn_stream_<name>` (taking the operands' dtype), or its bf16-MFMA twin."""
+    if cores == "f32":
+        return getattr(lib, "ea_attn_stream_" + name), (ops.dt(q),)
+    if cores != "bf16":
+        raise ValueError(f"cores={cores!r}: 'f32' or 'bf16'")
+    if q.dtype != torch.bfloat16:
+        raise NotImplementedError(f"cores='bf16' takes bf16 operands, not {str(q.dtype).replace('torch.', '')}")
+    return getattr(lib, "ea_attn_stream_bf16_" + name), ()
 
 
 def fused_attn_ok(cd, dk, T1, T2) -> bool:
@@ -81,10 +100,11 @@ def stream_attn_ok(cd, dk, T1, T2, need_grad) -> bool:
 
 
 def attn_stream_fwd(q, k, v, *, B, H, T1, T2, dk, ldq, ldk, ldv, klen, causal, scale, cd, p=0.0, bd=None, ldbd=0,
-                    rel_mode=0, lse=False):
+                    rel_mode=0, lse=False, cores="f32"):
     """ea_attn_stream_fwd: softmax(scale*(q k^T [+ rel_shift(bd)]) masked) @ v for all (b, h), keys
     walked in tiles with an online softmax (no (T1, T2) buffer; any T2; head dim a multiple of 8 up
-    to 128).  Operands as attn_fwd's (f32 or bf16 row views).  Forward only, no dropout.  Returns
+    to 128).  Operands as attn_fwd's (f32 or bf16 row views).  Forward only, no dropout.  cores: "f32"
+    multiplies on the f32 matrix cores; "bf16" (bf16 operands) on the bf16 ones, O written in bf16.  Returns
     O (B*T1, H*dk) in cd, or (O, lse (B*H*T1) f32) with lse=True."""
     if p > 0:
         raise NotImplementedError(f"attn_stream_fwd has no dropout (attention dropout rate {p}): it is the "
@@ -92,45 +112,47 @@ def attn_stream_fwd(q, k, v, *, B, H, T1, T2, dk, ldq, ldk, ldv, klen, causal, s
     if dk % 8 or not 8 <= dk <= 128:
         raise NotImplementedError(f"attn_stream_fwd: head dim {dk} is not a multiple of 8 in [8, 128]")
     dev = q.device
-    O = empty(B * T1, H * dk, device=dev)
+    fn, dt = _stream_entry("fwd", cores, q)
+    O = empty(B * T1, H * dk, dtype=q.dtype if cores == "bf16" else F32, device=dev)
     L = empty(B * H * T1, device=dev) if lse else None
-    lib.ea_attn_stream_fwd(B, H, T1, T2, dk, q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, ops.dt(q),
-                           ptr(bd), ldbd, ptr(klen), int(causal), float(scale), float(p), O.data_ptr(), H * dk,
-                           ptr(L), rel_mode, ops.stream())
-    if cd != F32:
+    fn(B, H, T1, T2, dk, q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, *dt, ptr(bd), ldbd, ptr(klen),
+       int(causal), float(scale), float(p), O.data_ptr(), H * dk, ptr(L), rel_mode, ops.stream())
+    if cd != O.dtype:
         O = ops.cast(O, cd)
     return (O, L) if lse else O
 
 
 def attn_stream_train_fwd(q, k, v, *, B, H, T1, T2, dk, ldq, ldk, ldv, klen, causal, scale, cd, p, seed, bd=None,
-                          ldbd=0, rel_mode=0):
+                          ldbd=0, rel_mode=0, cores="f32"):
     """ea_attn_stream_fwd_train: attn_stream_fwd with dropout on the probabilities, the keep law and
     salt of attn_fwd (the same (p, seed) drops the same elements).  Returns O (B*T1, H*dk) in cd and
     lse (B*H*T1) f32 of the undropped scores, what attn_stream_bwd needs beside the operands."""
     if dk % 8 or not 8 <= dk <= 128:
         raise NotImplementedError(f"attn_stream_train_fwd: head dim {dk} is not a multiple of 8 in [8, 128]")
     dev = q.device
-    O = empty(B * T1, H * dk, device=dev)
+    fn, dt = _stream_entry("fwd_train", cores, q)
+    O = empty(B * T1, H * dk, dtype=q.dtype if cores == "bf16" else F32, device=dev)
     L = empty(B * H * T1, device=dev)
-    lib.ea_attn_stream_fwd_train(B, H, T1, T2, dk, q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv,
-                                 ops.dt(q), ptr(bd), ldbd, ptr(klen), int(causal), float(scale), float(p), seed,
-                                 O.data_ptr(), H * dk, L.data_ptr(), rel_mode, ops.stream())
-    if cd != F32:
+    fn(B, H, T1, T2, dk, q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, *dt, ptr(bd), ldbd, ptr(klen),
+       int(causal), float(scale), float(p), seed, O.data_ptr(), H * dk, L.data_ptr(), rel_mode, ops.stream())
+    if cd != O.dtype:
         O = ops.cast(O, cd)
     return O, L
 
 
 def attn_stream_bwd(dO, q, k, v, lse, *, B, H, T1, T2, dk, ldq, ldk, ldv, klen, causal, scale, p, seed,
-                    dq, lddq, dk_, lddk, dv, lddv, bd=None, ldbd=0, dbd=None, lddbd=0, rel_mode=0):
+                    dq, lddq, dk_, lddk, dv, lddv, bd=None, ldbd=0, dbd=None, lddbd=0, rel_mode=0,
+                    cores="f32"):
     """ea_attn_stream_bwd: backward of attn_stream_train_fwd from its operands, lse and dO
     ((B*T1, H*dk) cd); the scores are recomputed, no (T1, T2) buffer.  Writes dq, dk_, dv (attn_bwd's
     contracts) and, with the raw band bd, its gradient dbd [h][b][i][lddbd] in cd, every one of the
     2*T1-1 columns.  The workspace (2*B*H*T1 f32) is a stream-ordered allocation."""
+    fn, dt = _stream_entry("bwd", cores, q)
     ws = empty(max(2 * B * H * T1, 1), device=dO.device)
-    lib.ea_attn_stream_bwd(B, H, T1, T2, dk, q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, ops.dt(q),
-                           ptr(bd), ldbd, ptr(klen), int(causal), float(scale), float(p), seed,
-                           lse.data_ptr(), dO.data_ptr(), H * dk, dq.data_ptr(), lddq, dk_.data_ptr(), lddk,
-                           dv.data_ptr(), lddv, ptr(dbd), lddbd, ws.data_ptr(), ws.numel() * 4, rel_mode, ops.stream())
+    fn(B, H, T1, T2, dk, q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, *dt, ptr(bd), ldbd, ptr(klen),
+       int(causal), float(scale), float(p), seed, lse.data_ptr(), dO.data_ptr(), H * dk, dq.data_ptr(), lddq,
+       dk_.data_ptr(), lddk, dv.data_ptr(), lddv, ptr(dbd), lddbd, ws.data_ptr(), ws.numel() * 4, rel_mode,
+       ops.stream())
 
 
 def attn_dmask(rows, T2, p, device):

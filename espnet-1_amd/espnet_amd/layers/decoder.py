@@ -18,7 +18,7 @@ from torch import nn
 from .common import (ACT_RELU, EPI_ACT, EPI_DACT, EPI_RESID, EPI_STORE, F32, Bound, attn_bwd,
                      attn_dmask, attn_fused_bwd, attn_fwd, attn_stream_bwd, attn_stream_fwd, attn_stream_train_fwd,
                      empty, fused_attn_ok, lib, ln_bwd, ln_fwd, ops, site_seed, dv_buf, drop_arg, site_dv,
-                     stream_attn_ok, stream_attn_train_ok)
+                     stream_attn_cores, stream_attn_ok, stream_attn_train_ok)
 
 
 def _mha_fwd(q, k, v, *, B, H, T1, T2, dk, ldq, ldk, ldv, klen, causal, scale, p, seed, cd, need_grad):
@@ -30,11 +30,12 @@ def _mha_fwd(q, k, v, *, B, H, T1, T2, dk, ldq, ldk, ldv, klen, causal, scale, p
     Returns (O, saved state)."""
     if stream_attn_train_ok(cd, dk, T1, T2, need_grad):
         O, lse = attn_stream_train_fwd(q, k, v, B=B, H=H, T1=T1, T2=T2, dk=dk, ldq=ldq, ldk=ldk, ldv=ldv, klen=klen,
-                                       causal=causal, scale=scale, cd=cd, p=p, seed=seed)
+                                       causal=causal, scale=scale, cd=cd, p=p, seed=seed,
+                                       cores=stream_attn_cores(cd))
         return O, ("stream_train", lse)
     if stream_attn_ok(cd, dk, T1, T2, need_grad):
         O = attn_stream_fwd(q, k, v, B=B, H=H, T1=T1, T2=T2, dk=dk, ldq=ldq, ldk=ldk, ldv=ldv, klen=klen,
-                            causal=causal, scale=scale, cd=cd, p=p)
+                            causal=causal, scale=scale, cd=cd, p=p, cores=stream_attn_cores(cd))
         return O, ("stream",)
     if fused_attn_ok(cd, dk, T1, T2):
         O = empty(B * T1, H * dk, dtype=cd, device=q.device)
@@ -61,7 +62,7 @@ def _mha_bwd(st, dO, q, k, v, *, B, H, T1, T2, dk, ldq, ldk, ldv, klen, causal, 
     if st[0] == "stream_train":
         attn_stream_bwd(dO, q, k, v, st[1], B=B, H=H, T1=T1, T2=T2, dk=dk, ldq=ldq, ldk=ldk, ldv=ldv, klen=klen,
                         causal=causal, scale=scale, p=p, seed=seed, dq=dq, lddq=lddq, dk_=dk_, lddk=lddk,
-                        dv=dv, lddv=lddv)
+                        dv=dv, lddv=lddv, cores=stream_attn_cores(cd))
         return
     _, P, Pd, ldT = st
     attn_bwd(dO, q, k, v, P, Pd, ldT, B=B, H=H, T1=T1, T2=T2, dk=dk, ldq=ldq, ldk=ldk, ldv=ldv, scale=scale,

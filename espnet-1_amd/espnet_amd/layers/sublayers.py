@@ -11,7 +11,7 @@ from __future__ import annotations
 
 from .common import (EPI_ACT, EPI_DACT, EPI_RESID, REL_LEGACY, attn_bwd, attn_dmask, attn_fused_bwd, attn_fwd,
                      attn_stream_bwd, attn_stream_fwd, attn_stream_train_fwd, dbd_layout, empty, fused_attn_ok, lib,
-                     ln_bwd, ln_fwd, math, ops, rup, site_dv, stream_attn_ok, stream_attn_train_ok)
+                     ln_bwd, ln_fwd, math, ops, rup, site_dv, stream_attn_cores, stream_attn_ok, stream_attn_train_ok)
 
 
 # ----------------------------------------------------------------------------- feed-forward
@@ -122,12 +122,13 @@ def rel_attn_fwd(b, A, xn, pos, olens, *, B, T, H, rel_mode, pa, seed, need_grad
         if stream:  # the band GEMM above, then one kernel that never builds the (T, T) scores
             O = attn_stream_fwd(qu, qkv[:, d:], qkv[:, 2 * d:], B=B, H=H, T1=T, T2=T, dk=dk, ldq=d, ldk=3 * d,
                                 ldv=3 * d, klen=olens, causal=False, scale=scale, cd=cd, p=pa, bd=bd, ldbd=ldbd,
-                                rel_mode=rel_mode)
+                                rel_mode=rel_mode, cores=stream_attn_cores(cd))
             return O, (qkv, pp, ("stream",), scale, 0)
         if train_stream:  # keeps q+u, q+v and lse; the band is recomputed in the backward
             O, lse = attn_stream_train_fwd(qu, qkv[:, d:], qkv[:, 2 * d:], B=B, H=H, T1=T, T2=T, dk=dk, ldq=d,
                                            ldk=3 * d, ldv=3 * d, klen=olens, causal=False, scale=scale, cd=cd, p=pa,
-                                           seed=seed, bd=bd, ldbd=ldbd, rel_mode=rel_mode)
+                                           seed=seed, bd=bd, ldbd=ldbd, rel_mode=rel_mode,
+                                           cores=stream_attn_cores(cd))
             return O, (qkv, pp, ("stream_train", qu, qv, lse), scale, 0)
         O, P, Pd, ldT = attn_fwd(qu, qkv[:, d:], qkv[:, 2 * d:], B=B, H=H, T1=T, T2=T, dk=dk,
                                  ldq=d, ldk=3 * d, ldv=3 * d, klen=olens, causal=False, scale=scale,
@@ -194,7 +195,8 @@ def rel_attn_bwd(b, A, dO, xn, O, saved, pos, olens, *, B, T, H, rel_mode, pa, s
             attn_stream_bwd(dO, qu, qkv[:, d:], qkv[:, 2 * d:], lse, B=B, H=H, T1=T, T2=T, dk=dk, ldq=d,
                             ldk=3 * d, ldv=3 * d, klen=olens, causal=False, scale=scale, p=pa, seed=seed,
                             dq=dqkv, lddq=3 * d, dk_=dqkv[:, d:], lddk=3 * d, dv=dqkv[:, 2 * d:], lddv=3 * d,
-                            bd=bd, ldbd=ldbd, dbd=dbd, lddbd=ldbd, rel_mode=rel_mode)
+                            bd=bd, ldbd=ldbd, dbd=dbd, lddbd=ldbd, rel_mode=rel_mode,
+                            cores=stream_attn_cores(cd))
             del bd
         else:
             _, qu, qv, P, Pd = s_core

@@ -667,6 +667,28 @@ int ea_attn_stream_bwd(int B, int H, int T1, int T2, int dk, const void* q, long
                        const float* lse, const void* dO, long lddo, void* dq, long lddq, void* dkout,
                        long lddk, void* dvout, long lddv, void* dbd, long lddbd,
                        float* ws, long ws_bytes, int rel_mode, void* stream);
+/* The three entry points above on the bf16 matrix cores (v_mfma_f32_16x16x32_bf16, f32 accumulation;
+ * csrc/attn_stream_bf16.hip): the same score law, masks, band indexing, dropout keep law and outputs, for
+ * bf16 operands only, so there is no `dtype`.  Scores, the running maximum and sum, lse and every accumulator
+ * are f32; the probabilities and dS are rounded to bf16 as MFMA operands.
+ *  q, k, v, dO: bf16, row strides % 8 == 0, 16-B aligned bases.  O (B*T1 rows of ldo), dq, dkout, dvout:
+ *    bf16, row strides % 4 == 0, 8-B aligned bases.  BD f32 and dbd bf16 as above; lse f32.
+ *  ws: B*H*T1 floats (the row sums D). */
+int ea_attn_stream_bf16_fwd(int B, int H, int T1, int T2, int dk, const void* q, long ldq, const void* k,
+                            long ldk, const void* v, long ldv, const float* BD, long ldBD,
+                            const long long* klen, int causal, float scale, float p, void* O, long ldo,
+                            float* lse, int rel_mode, void* stream);
+int ea_attn_stream_bf16_fwd_train(int B, int H, int T1, int T2, int dk, const void* q, long ldq,
+                                  const void* k, long ldk, const void* v, long ldv, const float* BD,
+                                  long ldBD, const long long* klen, int causal, float scale, float p,
+                                  unsigned long long seed, void* O, long ldo, float* lse, int rel_mode,
+                                  void* stream);
+int ea_attn_stream_bf16_bwd(int B, int H, int T1, int T2, int dk, const void* q, long ldq, const void* k,
+                            long ldk, const void* v, long ldv, const float* BD, long ldBD,
+                            const long long* klen, int causal, float scale, float p,
+                            unsigned long long seed, const float* lse, const void* dO, long lddo, void* dq,
+                            long lddq, void* dkout, long lddk, void* dvout, long lddv, void* dbd,
+                            long lddbd, float* ws, long ws_bytes, int rel_mode, void* stream);
 
 /* ---------------------------------------------------------------- losses */
 
